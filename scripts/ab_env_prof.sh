@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 for r in 1 2; do
   for v in $VALS; do
     export $VAR=$v
-    timeout -k 10 200 rocprofv3 --kernel-trace -d $OUT/${v}_$r -o run --output-format csv -- python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/${v}_$r.log 2>&1 || exit 1
+    timeout -k 10 200 rocprofv3 --kernel-trace -d $OUT/${v}_$r -o run --output-format csv -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $OUT/${v}_$r.log 2>&1 || exit 1
     python3 - "$OUT/${v}_$r" "$PAT" "$v" "$r" "$OUT/${v}_$r.log" <<'PY' | tee -a $OUT/summary.jsonl
 import csv, glob, json, statistics, sys
 d, pat, v, r, log = sys.argv[1:]

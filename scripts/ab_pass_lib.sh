@@ -11,7 +11,7 @@ for r in 1 2; do
     cp ab_$v.so $LIB
     timeout -k 10 200 python benchmarks/bench_pass.py --variants ${PASS_VARIANTS:-0,256} --finals 0,1 --reps 10 > $OUT/abp_${v}_$r.jsonl 2>&1 || { echo "pass $v $r failed"; tail -5 $OUT/abp_${v}_$r.jsonl; exit 1; }
     grep variant $OUT/abp_${v}_$r.jsonl | sed "s/^/$v $r /"
-    timeout -k 10 300 python bench.py --steps 30 --warmup 5 > $OUT/ab_${v}_$r.log 2>&1 || { echo "bench $v $r failed"; tail -5 $OUT/ab_${v}_$r.log; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 > $OUT/ab_${v}_$r.log 2>&1 || { echo "bench $v $r failed"; tail -5 $OUT/ab_${v}_$r.log; exit 1; }
     echo "$v $r bench $(tail -1 $OUT/ab_${v}_$r.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["step_ms"]["median"], d["check"]["ok"])')"
   done
 done

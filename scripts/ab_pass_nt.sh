@@ -9,7 +9,7 @@ timeout -k 10 200 python benchmarks/bench_pass.py --variants 0,512,256,768 --fin
 cat $OUT/ab_pass_nt_kernel.jsonl
 for r in 1 2; do
   for c in ${CODES:-0 1 3 5}; do
-    SL_PASS_NT=$c timeout -k 10 200 python bench.py --steps 40 --warmup 10 > $OUT/ab_nt_$c.log 2>&1 || exit 1
+    SL_PASS_NT=$c timeout -k 10 200 python bench.py --full --steps 40 --warmup 10 > $OUT/ab_nt_$c.log 2>&1 || exit 1
     python - "$c" "$r" $OUT/ab_nt_$c.log <<'PY' | tee -a $OUT/ab_pass_nt_bench.jsonl
 import json, sys
 d = json.loads(open(sys.argv[3]).read().strip().split("\n")[-1])

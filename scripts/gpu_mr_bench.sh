@@ -9,6 +9,6 @@ OUT=gpurun_out; mkdir -p $OUT
 bash scripts/gpu_mr.sh || exit 1
 for n in 2 4; do
   SKH_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port $((29600 + n)) bench.py --gpus $n --steps 5 --warmup 2 > $OUT/mr_bench_$n.log 2>&1
+    --master-port $((29600 + n)) bench.py --gpus $n --full --steps 5 --warmup 2 > $OUT/mr_bench_$n.log 2>&1
   rc=$?; grep '^{' $OUT/mr_bench_$n.log | cut -c1-400; [ $rc -eq 0 ] || { tail -20 $OUT/mr_bench_$n.log; exit $rc; }
 done

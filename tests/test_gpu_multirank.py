@@ -103,7 +103,8 @@ def _rank_bench(rank, world):
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     a = types.SimpleNamespace(rows=60000, cols=512, rank=20, iters=2, sketch="FJLT", scaling="strong",
-                              layout="MC_MR", tile_rows=4096, tile_cols=128, grid_rows=0, steps=3, warmup=2)
+                              layout="MC_MR", tile_rows=4096, tile_cols=128, grid_rows=0, steps=3, warmup=2,
+                              full=True, dump_outputs=None)     # --full: the answer check is what is asserted
     comm = Comm()
     dev = torch.device("cuda", 0)
     out = {}
