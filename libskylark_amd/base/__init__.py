@@ -2,7 +2,7 @@
 random matrices, sparse matrices, cross-type BLAS, parameters."""
 from . import distributions, exceptions, quasirand  # noqa: F401
 from .blas import (QR, Axpy, ColumnView, ComputedMatrix, DenseCopy, ExplicitUnitary, Gemm, Gemv,  # noqa: F401
-                   Height, RowDot, RowView, Scale, Symm, Trsm, Width)
+                   Height, Herk, MakeSymmetric, RowDot, RowView, Scale, Symm, Syrk, Trsm, Width)
 from .context import Context, RandomSamplesArray  # noqa: F401
 from .exceptions import *  # noqa: F401,F403
 from .params import Params, print_matrix  # noqa: F401

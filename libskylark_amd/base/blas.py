@@ -296,6 +296,100 @@ def Symm(side: str, uplo: str, alpha, A, B, beta=0.0, C=None):
     return Gemm("N", "N", alpha, B, S, beta, C)
 
 
+def _tri_mask(s: int, uplo: str, device) -> torch.Tensor:
+    ones = torch.ones(s, s, dtype=torch.bool, device=device)
+    return torch.tril(ones) if uplo == "L" else torch.triu(ones)
+
+
+def _tri_update(C: torch.Tensor, uplo: str, P: torch.Tensor, beta) -> torch.Tensor:
+    """``uplo`` triangle of C <- P + beta C; the other triangle keeps its bits
+    and ``beta == 0`` takes nothing from C."""
+    new = P.to(C.dtype) if beta == 0.0 else (C * beta).add_(P.to(C.dtype))
+    C.copy_(torch.where(_tri_mask(C.shape[0], uplo, C.device), new, C))
+    return C
+
+
+def _herk_local(uplo: str, trans: bool, alpha, A: torch.Tensor, beta, C: torch.Tensor | None) -> torch.Tensor:
+    if A.layout != torch.strided:
+        A = A.to_dense()
+    s, k = (A.shape[1], A.shape[0]) if trans else A.shape
+    if C is None:
+        C = torch.zeros(s, s, dtype=A.dtype, device=A.device)
+        beta = 0.0
+    elif C.dim() != 2 or tuple(C.shape) != (s, s):
+        raise DimensionMismatchError(f"Herk: C is {tuple(C.shape)}, op(A) op(A)^T is {(s, s)}")
+    from ..ops import syrk
+    An, tn = A, trans
+    if A.is_cuda and k > 0 and s > 0:
+        if A.dtype == torch.float32 and A.stride(1) != 1:
+            # a column-major A is the row-major operand of the other orientation
+            An, tn = (A.t(), not trans) if A.stride(0) == 1 else (A.contiguous(), trans)
+        elif A.dtype == torch.bfloat16 and not trans and not syrk.takes(A, trans=False):
+            An = torch.nn.functional.pad(A, (0, -k % 64)).contiguous()   # zero K columns, 16-B aligned rows
+    if not (k > 0 and s > 0 and syrk.takes(An, trans=tn)):
+        # f64, bf16 A^T A, CPU: a product in the operand's precision
+        Ah = A.t().conj() if A.is_complex() else A.t()
+        P = Ah @ A if trans else A @ Ah
+        return _tri_update(C, uplo, P * alpha if alpha != 1.0 else P, beta)
+    # a GPU operand the kernel takes: the native library is mandatory there
+    # (ops/_lib.py), a missing one raises rather than falling back
+    if syrk.takes(An, C, trans=tn):
+        return syrk.syrk_split(An, C, trans=tn, uplo=uplo, alpha=alpha, beta=beta)
+    P = syrk.syrk_split(An, None, trans=tn, uplo=uplo, alpha=alpha)
+    return _tri_update(C, uplo, P.to(C.device), beta)
+
+
+def Herk(uplo: str, orient: str, alpha, A, beta=0.0, C=None):
+    """The ``uplo`` triangle of ``C = alpha A A^T + beta C`` (orient N) or
+    ``alpha A^T A + beta C`` (orient T / C), Elemental's ``Herk`` (reference
+    call sites ``ml/krr.hpp:371``, ``ml/kernels.hpp:241``,
+    ``base/distance.hpp:92``).  Only that triangle of C is referenced or
+    written; ``C=None`` allocates zeros in A's dtype.  Returns C.
+
+    f32 A on the GPU (either orientation) and bf16 A on the GPU with orient N
+    run the native triangular kernel (``ops/syrk.py``: exact bf16-split
+    products, f64 across row chunks); every other local case is a torch
+    product in the operand's precision written through a triangle mask.
+    ``[VC,*]`` A with orient T: local Herk + one all-reduce of the s x s
+    block, replicated result; other distributed layouts are gathered."""
+    up, o = str(uplo).upper(), str(orient).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if o not in ("N", "T", "C"):
+        raise ValueError(f"orientation must be N, T or C (got {orient})")
+    Ct = C.local if _is_dist(C) else C
+    if _is_dist(A):
+        from ..parallel.distmatrix import is_row_dist
+        if o != "N" and is_row_dist(A.layout):
+            P = _herk_local(up, True, 1.0, _as_tensor(A.local), 0.0, None).contiguous()
+            A.comm.all_reduce(P)
+            if alpha != 1.0:
+                P = P * alpha
+            if Ct is None:
+                return P
+            if tuple(Ct.shape) != tuple(P.shape):
+                raise DimensionMismatchError(f"Herk: C is {tuple(Ct.shape)}, op(A) op(A)^T is {tuple(P.shape)}")
+            _tri_update(Ct, up, P, beta)
+            return C
+        A = A.to_global()
+    out = _herk_local(up, o != "N", alpha, _as_tensor(A), beta, Ct)
+    return out if C is None else C
+
+
+Syrk = Herk
+
+
+def MakeSymmetric(uplo: str, C):
+    """Copy the stored ``uplo`` triangle of C over the other one, in place."""
+    up = str(uplo).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    Ct = C.local if _is_dist(C) else C
+    other = Ct.t().conj() if Ct.is_complex() else Ct.t()
+    Ct.copy_(torch.where(_tri_mask(Ct.shape[0], up, Ct.device), Ct, other))
+    return C
+
+
 def _dist_left(S, alpha, B, beta, C):
     """Replicated symmetric S times a distributed B (all-gather B once)."""
     from ..parallel.distmatrix import DistMatrix
@@ -415,5 +509,5 @@ def RowDot(X, Y) -> torch.Tensor:
     return (Xl * Yl).sum(1)
 
 
-__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Trsm", "ExplicitUnitary", "QR", "Axpy", "Scale",
+__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "ExplicitUnitary", "QR", "Axpy", "Scale",
            "ColumnView", "RowView", "DenseCopy", "RowDot", "Height", "Width"]

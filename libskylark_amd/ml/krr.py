@@ -189,7 +189,14 @@ def _ridge(Z: torch.Tensor, Y: torch.Tensor, lam: float, data: _Data | None = No
     from ..ops import normal_eq
     if split:
         Gzz = torch.zeros(s, s, dtype=torch.float64, device=Z.device)
-        _gram_split(Z, Gzz)
+        if os.environ.get("SKH_KRR_GRAM", "") == "syrk":
+            # opt-in: the lower triangle only, from the native triangular
+            # kernel (ops/syrk.py); the Cholesky below reads nothing else and
+            # the zero upper triangle passes through the all-reduce unchanged
+            from ..base.blas import Herk
+            Herk("L", "T", 1.0, Z, C=Gzz)
+        else:
+            _gram_split(Z, Gzz)
         G[:, :s] = Gzz
     if split and normal_eq.native_ok(Z, t) and Y2.shape[0] == Z.shape[0]:
         # Z^T Y from one streaming read of Z (ata_kernels.hip dual pass: f32
