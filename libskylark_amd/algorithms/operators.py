@@ -139,6 +139,59 @@ class DenseOp(Operator):
         return super().normal(X, want_y)
 
 
+class SymTriOp(Operator):
+    """Square symmetric A of which only the ``uplo`` triangle is stored
+    (Elemental's ``Symm`` contract, ``base/Symm.hpp``): the other triangle is
+    never used and may hold anything.  ``A^T`` is ``A``.  On the GPU the
+    product runs the triangle-reading kernel (``ops/symm.py``), which streams
+    half the bytes of a full product, in column groups of 8; on the CPU the
+    triangle is mirrored in torch.  dtype, shape and the inner products are
+    those of :class:`DenseOp`, so ``cg`` / ``flexible_cg`` take it unchanged."""
+
+    GROUP = 8
+
+    def __init__(self, A: torch.Tensor, uplo: str = "L"):
+        up = str(uplo).upper()
+        if up not in ("L", "U"):
+            raise ValueError(f"uplo must be L or U (got {uplo})")
+        if A.dim() != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError(f"SymTriOp needs a square matrix (got {tuple(A.shape)})")
+        cdt = A.dtype if A.dtype in (torch.float32, torch.float64) else torch.float32
+        super().__init__(A.shape, cdt, A.device)
+        self.A = A
+        self.uplo = up
+        if A.is_cuda:
+            from ..ops import symm as _sy
+            # the kernel's view: a column-major A is the transpose with the other triangle
+            self._An, self._un = (A.t(), "U" if up == "L" else "L") if A.stride(1) != 1 and A.stride(0) == 1 else (A, up)
+            why = _sy._why_not(self._An)
+            if why is not None:
+                raise ValueError(f"SymTriOp: {why}")
+
+    def _full(self):
+        tri = torch.tril(self.A) if self.uplo == "L" else torch.triu(self.A)
+        strict = torch.tril(self.A, -1) if self.uplo == "L" else torch.triu(self.A, 1)
+        return (tri + strict.t()).to(self.dtype)
+
+    def matmul(self, X):
+        vec = X.dim() == 1
+        X2 = (X[:, None] if vec else X).to(self.dtype)
+        if not self.A.is_cuda:
+            Y = self._full() @ X2
+            return Y[:, 0] if vec else Y
+        from ..ops import symm as _sy
+        k = X2.shape[1]
+        if k <= self.GROUP:
+            Y = _sy.symm_tri(self._An, X2, uplo=self._un)
+        else:
+            Y = torch.empty(self.shape[0], k, dtype=self.dtype, device=self.device)
+            for c0 in range(0, k, self.GROUP):
+                Y[:, c0:c0 + self.GROUP] = _sy.symm_tri(self._An, X2[:, c0:c0 + self.GROUP], uplo=self._un)
+        return Y[:, 0] if vec else Y
+
+    rmatmul = matmul
+
+
 class SparseOp(Operator):
     def __init__(self, A: torch.Tensor):
         vdt = A.values().dtype

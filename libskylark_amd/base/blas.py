@@ -280,9 +280,54 @@ def Gemv(oA: str, alpha, A, x, beta=0.0, y=None):
     return r.reshape(-1) if not (hasattr(x, "dim") and x.dim() == 2) else r
 
 
+def _symm_native(side: str, uplo: str, alpha, A, B, beta, C):
+    """The triangle-reading kernel (``ops/symm.py``) for a local dense A and
+    at most 8 right-hand sides; ``None`` when the operands are not its own."""
+    from ..ops import symm as _sy
+    if not (isinstance(A, torch.Tensor) and isinstance(B, torch.Tensor) and A.dim() == 2 and B.dim() == 2
+            and A.shape[0] == A.shape[1] and (C is None or isinstance(C, torch.Tensor))):
+        return None
+    up = uplo.upper()
+    if A.stride(1) != 1 and A.stride(0) == 1:
+        # a column-major A is the row-major transpose with the other triangle stored
+        A, up = A.t(), ("U" if up == "L" else "L")
+    X = B if side.upper() == "L" else B.t()          # B A = (A B^T)^T for symmetric A
+    if up not in ("L", "U") or not _sy.takes(A, X):
+        return None
+    if C is None:
+        Y = _sy.symm_tri(A, X, uplo=up, alpha=alpha)
+        return Y if side.upper() == "L" else Y.t()
+    Ct = C if side.upper() == "L" else C.t()
+    if tuple(Ct.shape) != (A.shape[0], X.shape[1]):
+        raise DimensionMismatchError(f"Symm: C is {tuple(C.shape)}, the product {(A.shape[0], X.shape[1])}")
+    if Ct.dtype == A.dtype and Ct.device == A.device and Ct.stride(1) == 1 and (
+            Ct.shape[0] == 1 or Ct.stride(0) >= Ct.shape[1]):
+        _sy.symm_tri(A, X, uplo=up, alpha=alpha, beta=beta, out=Ct)
+        return C
+    Y = _sy.symm_tri(A, X, uplo=up, alpha=alpha)
+    if beta == 0.0:
+        Ct.copy_(Y)
+    else:
+        Ct.mul_(beta).add_(Y.to(Ct.dtype))
+    return C
+
+
 def Symm(side: str, uplo: str, alpha, A, B, beta=0.0, C=None):
-    """``C = alpha A B + beta C`` (side L) or ``alpha B A`` (side R) with
-    symmetric A stored in its ``uplo`` triangle (``base/Symm.hpp``)."""
+    """``C = alpha A B + beta C`` (side L) or ``alpha B A + beta C`` (side R)
+    with symmetric A stored in its ``uplo`` triangle (``base/Symm.hpp``);
+    the other triangle is never used.
+
+    A local dense f32 / f64 A on the GPU with 16-B aligned rows (row- or
+    column-major) and a local B of at most 8 columns (side L) or rows (side
+    R) run the native triangle-reading kernel (``ops/symm.py``): one pass
+    over the stored triangle, no n x n temporary, f32 sums inside 256 x 256
+    tiles and f64 across them.  Every other operand (distributed, sparse,
+    CPU, wider B, unaligned A, other dtypes) forms the full symmetric matrix
+    from the triangle (three n x n temporaries) and calls ``Gemm``."""
+    if not _is_dist(A) and not _is_dist(B) and not _is_dist(C):
+        out = _symm_native(side, uplo, alpha, A, B, beta, C)
+        if out is not None:
+            return out
     if _is_dist(A):
         Af = A.to_global()
     else:

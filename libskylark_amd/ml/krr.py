@@ -32,7 +32,7 @@ from dataclasses import dataclass
 import torch
 
 from ..algorithms.krylov import CallablePrecond, IdPrecond, KrylovIterParams, cg
-from ..algorithms.operators import DenseOp, DistSymOp
+from ..algorithms.operators import DenseOp, DistSymOp, SymTriOp
 from ..base.context import Context
 from ..parallel.comm import Comm
 from ..parallel.distmatrix import DistMatrix
@@ -443,7 +443,9 @@ def faster_kernel_ridge(k: Kernel, X, Y, lam: float, s: int, context: Context | 
     else:
         K = k.symmetric_gram(data.local)
         K.diagonal().add_(lam)
-        op = DenseOp(K)
+        # SKH_KRR_SYMM=tri: the CG product reads only the lower triangle of K
+        # (ops/symm.py, half the bytes per iteration); the default streams all of it
+        op = SymTriOp(K, "L") if os.environ.get("SKH_KRR_SYMM", "").lower() == "tri" else DenseOp(K)
     _log(p, 1, "Creating preconditioner...")
     if s == 0:
         P = IdPrecond()
