@@ -1,8 +1,9 @@
 """Base layer: context, random streams, distributions, QMC, exceptions,
 random matrices, sparse matrices, cross-type BLAS, parameters."""
 from . import distributions, exceptions, quasirand  # noqa: F401
-from .blas import (QR, Axpy, ColumnView, ComputedMatrix, DenseCopy, ExplicitUnitary, Gemm, Gemv,  # noqa: F401
-                   Height, Herk, MakeSymmetric, RowDot, RowView, Scale, Symm, Syrk, Trsm, Width)
+from .blas import (QR, Axpy, Cholesky, CholeskySolveAfter, ColumnView, ComputedMatrix, DenseCopy,  # noqa: F401
+                   ExplicitUnitary, Gemm, Gemv, Height, Herk, HPDSolve, MakeSymmetric, RowDot, RowView, Scale, Symm,
+                   Syrk, Trsm, Width)
 from .context import Context, RandomSamplesArray  # noqa: F401
 from .exceptions import *  # noqa: F401,F403
 from .params import Params, print_matrix  # noqa: F401

@@ -1,5 +1,6 @@
 """Cross-type dense / sparse / distributed BLAS: ``Gemm``, ``Gemv``, ``Symm``,
-``Trsm``, explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
+``Herk``, ``Cholesky`` / ``CholeskySolveAfter`` / ``HPDSolve``, ``Trsm``,
+explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
 
 Reference: ``base/Gemm.hpp:19-583`` (local dense, sparse x dense in all four
 orientations, ``[VC,*]^T [VC,*] -> [*,*]`` by local GEMM + all-reduce
@@ -468,6 +469,107 @@ def Trsm(side: str, uplo: str, orient: str, diag: str, alpha, A, B):
     return B
 
 
+def _cholesky_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
+    from ..ops import cholesky as _ch
+    from .exceptions import NLAError
+    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatchError(f"Cholesky: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    An, un = A, up
+    if A.shape[1] > 1 and A.stride(1) != 1 and A.stride(0) == 1:
+        # a column-major A is the row-major transpose with the other triangle stored
+        An, un = A.t(), ("U" if up == "L" else "L")
+    if _ch.takes(An):
+        # a GPU operand the kernel takes: the native library is mandatory there
+        # (ops/_lib.py), a missing one raises rather than falling back
+        _ch.chol_tri(An, un, info)
+        return A
+    S = torch.where(_tri_mask(A.shape[0], up, A.device), A, torch.zeros((), dtype=A.dtype, device=A.device))
+    F, linfo = torch.linalg.cholesky_ex(S, upper=up == "U")
+    _tri_update(A, up, F, 0.0)
+    if info is not None:
+        info.copy_(linfo.reshape(info.shape))
+    else:
+        p = int(linfo.item())
+        if p != 0:
+            raise NLAError(f"Cholesky: the matrix is not positive definite: pivot {p} (1-based) "
+                           f"is not positive and finite")
+    return A
+
+
+def Cholesky(uplo: str, A, info=None):
+    """Overwrite the ``uplo`` triangle of the Hermitian positive definite A
+    with its Cholesky factor, ``A = L L^H`` (L) or ``A = U^H U`` (U):
+    Elemental's ``Cholesky`` (reference call sites ``ml/krr.hpp:372``,
+    ``:640``).  Only that triangle is read or written; the other one keeps its
+    bits and may hold anything.  Returns A.
+
+    A local f64 matrix on the GPU with unit stride along rows or columns runs
+    the native blocked kernel (``ops/cholesky.py``: substitution panel solves,
+    trailing updates on the f64 matrix cores, no n x n temporary).  Every
+    other local operand (CPU, f32, complex, views with neither unit stride)
+    goes through ``torch.linalg.cholesky_ex`` on a masked copy.  A ``[*,*]``
+    DistMatrix is factored on every rank; distributed layouts raise
+    :class:`UnsupportedBaseOperation`.
+
+    A pivot that is not positive raises :class:`NLAError` naming its 1-based
+    index, unless ``info`` (an int32 one-element tensor on A's device) is
+    given: then the index (0: none) is left there without a host
+    synchronisation and nothing is raised."""
+    up = str(uplo).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if _is_dist(A):
+        if A.layout != "STAR_STAR":
+            raise UnsupportedBaseOperation(f"Cholesky of a {A.layout} matrix (only [*,*] and local)")
+        _cholesky_local(up, A.local, info)
+        return A
+    _cholesky_local(up, _as_tensor(A), info)
+    return A
+
+
+def CholeskySolveAfter(uplo: str, orient: str, F, B):
+    """Solve ``A X = B`` in place on B from the Cholesky factor of A in the
+    ``uplo`` triangle of F (Elemental's ``cholesky::SolveAfter``, reference
+    ``ml/krr.hpp:398``, ``:650``): two triangular solves through :func:`Trsm`
+    (``torch.linalg.solve_triangular``).  Only that triangle of F matters: the
+    library solve gives finite, bit-equal solutions with NaN in the other one
+    on the CPU and on the GPU (``tests/test_gpu_chol.py``), so F is not masked
+    into a temporary.  ``orient`` N, or T / C for real data (A is symmetric); B local or a
+    DistMatrix with replicated rows.  Returns B."""
+    up, o = str(uplo).upper(), str(orient).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if o not in ("N", "T", "C"):
+        raise ValueError(f"orientation must be N, T or C (got {orient})")
+    Fl = F.local if _is_dist(F) else _as_tensor(F)
+    if _is_dist(F) and F.layout != "STAR_STAR":
+        raise UnsupportedBaseOperation(f"CholeskySolveAfter with a {F.layout} factor (only [*,*] and local)")
+    if Fl.dim() != 2 or Fl.shape[0] != Fl.shape[1] or Height(B) != Fl.shape[0]:
+        raise DimensionMismatchError(f"CholeskySolveAfter: F is {tuple(Fl.shape)}, B has {Height(B)} rows")
+    if Fl.is_complex():
+        if o == "T":
+            raise UnsupportedBaseOperation("CholeskySolveAfter with orient T on complex data")
+        Fh = Fl.conj()            # Trsm's T does not conjugate
+    else:
+        Fh = Fl
+    if up == "L":
+        Trsm("L", "L", "N", "N", 1.0, Fl, B)
+        Trsm("L", "L", "T", "N", 1.0, Fh, B)
+    else:
+        Trsm("L", "U", "T", "N", 1.0, Fh, B)
+        Trsm("L", "U", "N", "N", 1.0, Fl, B)
+    return B
+
+
+def HPDSolve(uplo: str, orient: str, A, B):
+    """``A X = B`` for Hermitian positive definite A stored in its ``uplo``
+    triangle (Elemental's ``HPDSolve``): :func:`Cholesky` then
+    :func:`CholeskySolveAfter`.  A ends as the factor, B as the solution;
+    returns B."""
+    Cholesky(uplo, A)
+    return CholeskySolveAfter(uplo, orient, A, B)
+
+
 def ExplicitUnitary(A):
     """Overwrite A with the Q factor of its QR (``base/QR.hpp:11-36``): TSQR for
     ``[VC,*]`` (one all-gather of the k x k R factors), Householder locally."""
@@ -554,5 +656,6 @@ def RowDot(X, Y) -> torch.Tensor:
     return (Xl * Yl).sum(1)
 
 
-__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "ExplicitUnitary", "QR", "Axpy", "Scale",
+__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "Cholesky", "CholeskySolveAfter", "HPDSolve",
+           "ExplicitUnitary", "QR", "Axpy", "Scale",
            "ColumnView", "RowView", "DenseCopy", "RowDot", "Height", "Width"]

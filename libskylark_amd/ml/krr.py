@@ -213,6 +213,12 @@ def _ridge(Z: torch.Tensor, Y: torch.Tensor, lam: float, data: _Data | None = No
         data.allreduce(G)
     C = G[:, :s]
     C.diagonal().add_(lam)
+    if os.environ.get("SKH_KRR_CHOL", "") == "native":
+        # opt-in: factor and solve from the lower triangle alone (base.Cholesky:
+        # the native one-triangle kernel on the GPU); with SKH_KRR_GRAM=syrk
+        # nothing from Gram to weights touches the upper triangle
+        from ..base.blas import HPDSolve
+        return HPDSolve("L", "N", C, G[:, s:])
     Lc = torch.linalg.cholesky(C)
     return torch.cholesky_solve(G[:, s:], Lc)
 
@@ -241,6 +247,9 @@ def kernel_ridge(k: Kernel, X, Y, lam: float, direction="rows", params: KrrParam
     K = K.to(dt)
     K.diagonal().add_(lam)
     _log(p, 1, "Solving the equation...")
+    if os.environ.get("SKH_KRR_CHOL", "") == "native":
+        from ..base.blas import HPDSolve
+        return HPDSolve("L", "N", K, Yg.to(dt, copy=True))
     Lc = torch.linalg.cholesky(K)
     A = torch.cholesky_solve(Yg.to(dt), Lc)
     return A
