@@ -450,21 +450,38 @@ def _dist_left(S, alpha, B, beta, C):
 
 def Trsm(side: str, uplo: str, orient: str, diag: str, alpha, A, B):
     """Triangular solve in place on B: ``op(A) X = alpha B`` (side L) or
-    ``X op(A) = alpha B`` (side R) (``base/Trsm.hpp``); A replicated."""
+    ``X op(A) = alpha B`` (side R) (``base/Trsm.hpp``); A replicated.  Only
+    the ``uplo`` triangle of A is read.
+
+    A local (or ``[*,*]``) f64 A on the GPU and a local f64 block of B, each
+    with unit stride along rows or columns, run the native blocked kernel
+    (``ops/trsm.py``, ``trsm_tri.hip``): in place, no ``alpha B`` temporary,
+    no allocation, the other triangle (and with diag U the diagonal) never
+    touched, bit-identical from run to run.  The native library is mandatory
+    there.  Every other operand (CPU, f32, complex, mixed dtypes, views with
+    neither unit stride, a tensor ``alpha``) goes through
+    ``torch.linalg.solve_triangular`` as before."""
+    from ..ops import trsm as _tr
     Af = A.to_global() if _is_dist(A) else _as_tensor(A)
+    Bt = B.local if _is_dist(B) else B
+    left = side.upper() == "L"
+    if left:
+        if _is_dist(B) and B.layout not in ("STAR_STAR", "STAR_VC", "STAR_VR"):
+            raise UnsupportedBaseOperation("Trsm left needs the rows of B replicated")
+    else:
+        if _is_dist(B) and B.layout not in ("STAR_STAR", "VC_STAR", "VR_STAR"):
+            raise UnsupportedBaseOperation("Trsm right needs the columns of B replicated")
+    if (isinstance(alpha, (int, float)) and side.upper() in ("L", "R") and _tr.takes(side, Af, Bt)
+            and _tr.regime(side, Bt) in _tr.BASE_NATIVE_REGIMES):
+        # GPU operands the kernel takes: the native library is mandatory there
+        # (ops/_lib.py), a missing one raises rather than falling back
+        _tr.trsm_tri(side, uplo, orient, diag, alpha, Af, Bt)
+        return B
     upper = uplo.upper() == "U"
     unit = diag.upper() == "U"
     if orient.upper() != "N":
         Af, upper = Af.t(), not upper
-    Bt = B.local if _is_dist(B) else B
-    if side.upper() == "L":
-        if _is_dist(B) and B.layout not in ("STAR_STAR", "STAR_VC", "STAR_VR"):
-            raise UnsupportedBaseOperation("Trsm left needs the rows of B replicated")
-        X = torch.linalg.solve_triangular(Af.to(Bt.dtype), alpha * Bt, upper=upper, left=True, unitriangular=unit)
-    else:
-        if _is_dist(B) and B.layout not in ("STAR_STAR", "VC_STAR", "VR_STAR"):
-            raise UnsupportedBaseOperation("Trsm right needs the columns of B replicated")
-        X = torch.linalg.solve_triangular(Af.to(Bt.dtype), alpha * Bt, upper=upper, left=False, unitriangular=unit)
+    X = torch.linalg.solve_triangular(Af.to(Bt.dtype), alpha * Bt, upper=upper, left=left, unitriangular=unit)
     Bt.copy_(X)
     return B
 
@@ -530,11 +547,12 @@ def Cholesky(uplo: str, A, info=None):
 def CholeskySolveAfter(uplo: str, orient: str, F, B):
     """Solve ``A X = B`` in place on B from the Cholesky factor of A in the
     ``uplo`` triangle of F (Elemental's ``cholesky::SolveAfter``, reference
-    ``ml/krr.hpp:398``, ``:650``): two triangular solves through :func:`Trsm`
-    (``torch.linalg.solve_triangular``).  Only that triangle of F matters: the
-    library solve gives finite, bit-equal solutions with NaN in the other one
-    on the CPU and on the GPU (``tests/test_gpu_chol.py``), so F is not masked
-    into a temporary.  ``orient`` N, or T / C for real data (A is symmetric); B local or a
+    ``ml/krr.hpp:398``, ``:650``): two triangular solves through :func:`Trsm`.
+    For f64 operands on the GPU both run the native kernel (``trsm_tri.hip``),
+    which cannot read the other triangle of F; elsewhere the library solve
+    gives finite, bit-equal solutions with NaN there
+    (``tests/test_gpu_chol.py``), so F is never masked into a temporary.
+    ``orient`` N, or T / C for real data (A is symmetric); B local or a
     DistMatrix with replicated rows.  Returns B."""
     up, o = str(uplo).upper(), str(orient).upper()
     if up not in ("L", "U"):
@@ -565,7 +583,8 @@ def HPDSolve(uplo: str, orient: str, A, B):
     """``A X = B`` for Hermitian positive definite A stored in its ``uplo``
     triangle (Elemental's ``HPDSolve``): :func:`Cholesky` then
     :func:`CholeskySolveAfter`.  A ends as the factor, B as the solution;
-    returns B."""
+    returns B.  With f64 operands on the GPU the whole chain is native and
+    reads one triangle only (``chol_tri.hip``, ``trsm_tri.hip``)."""
     Cholesky(uplo, A)
     return CholeskySolveAfter(uplo, orient, A, B)
 
