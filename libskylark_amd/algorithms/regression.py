@@ -25,6 +25,7 @@ redundant on every GPU, LSQR/Chebyshev use the distributed operator.
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -222,7 +223,17 @@ def _tri_inv_upper(R: torch.Tensor, block: int = 1024) -> torch.Tensor:
     """R^{-1} of an upper-triangular R, one column block at a time (column
     block j of R^{-1} only involves the leading j1 x j1 block of R; blocking
     also bounds the BLAS trsm workspace, which failed to allocate for a single
-    5000-column right-hand side on the MI355X)."""
+    5000-column right-hand side on the MI355X).
+
+    Opt-in, read at call time: with ``SKH_LS_TRINV=native`` an f64 R on the GPU
+    that the one-triangle kernel takes is cloned and inverted in place by
+    ``base.TriangularInverse("U", "N", clone)`` (``trtri_tri.hip``); the exact
+    zeros below R's diagonal are cloned and left alone."""
+    if os.environ.get("SKH_LS_TRINV", "") == "native":
+        from ..base.blas import TriangularInverse
+        from ..ops import trtri as _ti
+        if _ti.takes(R):
+            return TriangularInverse("U", "N", R.clone())
     n = R.shape[0]
     Rinv = torch.zeros_like(R)
     for j0 in range(0, n, block):

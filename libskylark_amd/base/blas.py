@@ -1,6 +1,6 @@
 """Cross-type dense / sparse / distributed BLAS: ``Gemm``, ``Gemv``, ``Symm``,
 ``Herk``, ``Cholesky`` / ``CholeskySolveAfter`` / ``HPDSolve``, ``Trsm``,
-explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
+``TriangularInverse``, explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
 
 Reference: ``base/Gemm.hpp:19-583`` (local dense, sparse x dense in all four
 orientations, ``[VC,*]^T [VC,*] -> [*,*]`` by local GEMM + all-reduce
@@ -486,6 +486,61 @@ def Trsm(side: str, uplo: str, orient: str, diag: str, alpha, A, B):
     return B
 
 
+def _triangular_inverse_local(up: str, dg: str, A: torch.Tensor) -> torch.Tensor:
+    from ..ops import trtri as _ti
+    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatchError(
+            f"TriangularInverse: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    if _ti.takes(A):
+        # a GPU operand the kernel takes: the native library is mandatory there
+        # (ops/_lib.py), a missing one raises rather than falling back
+        _ti.trtri_tri(up, dg, A)
+        return A
+    n = A.shape[0]
+    if n == 0:
+        return A
+    mask = _tri_mask(n, up, A.device)
+    eye = torch.eye(n, dtype=A.dtype, device=A.device)
+    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+    if dg == "U":
+        mask = mask & ~eye.bool()
+        S = torch.where(mask, S, eye)
+    X = torch.linalg.solve_triangular(S, eye, upper=up == "U", unitriangular=dg == "U")
+    A.copy_(torch.where(mask, X, A))
+    return A
+
+
+def TriangularInverse(uplo: str, diag: str, A):
+    """Overwrite the ``uplo`` triangle of the triangular A with the same
+    triangle of its inverse: Elemental's ``TriangularInverse`` (reference call
+    site ``algorithms/regression/accelerated_linearl2_regression_solver_Elemental.hpp:63``,
+    the explicit ``R^-1`` of Blendenpik / LSRN).  Only that triangle is read or
+    written, and with diag U not its diagonal, which is taken as ones; the
+    rest keeps its bits and may hold anything.  Returns A.
+
+    A local f64 matrix on the GPU with unit stride along rows or columns runs
+    the native blocked kernel (``ops/trtri.py``, ``trtri_tri.hip``): in place,
+    ``n^3 / 3`` flops, no identity, no second n x n buffer, no allocation,
+    bit-identical from run to run.  The native library is mandatory there.
+    Every other local operand (CPU, f32, complex, views with neither unit
+    stride) goes through ``torch.linalg.solve_triangular`` on a masked copy
+    against the identity, written back through the triangle mask.  A ``[*,*]``
+    DistMatrix is inverted on every rank; distributed layouts raise
+    :class:`UnsupportedBaseOperation`."""
+    up, dg = str(uplo).upper(), str(diag).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if dg not in ("N", "U"):
+        raise ValueError(f"diag must be N or U (got {diag})")
+    if _is_dist(A):
+        if A.layout != "STAR_STAR":
+            raise UnsupportedBaseOperation(f"TriangularInverse of a {A.layout} matrix (only [*,*] and local)")
+        _triangular_inverse_local(up, dg, A.local)
+        return A
+    _triangular_inverse_local(up, dg, _as_tensor(A))
+    return A
+
+
 def _cholesky_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
     from ..ops import cholesky as _ch
     from .exceptions import NLAError
@@ -675,6 +730,6 @@ def RowDot(X, Y) -> torch.Tensor:
     return (Xl * Yl).sum(1)
 
 
-__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "Cholesky", "CholeskySolveAfter", "HPDSolve",
+__all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "TriangularInverse", "Cholesky", "CholeskySolveAfter", "HPDSolve",
            "ExplicitUnitary", "QR", "Axpy", "Scale",
            "ColumnView", "RowView", "DenseCopy", "RowDot", "Height", "Width"]
