@@ -1319,14 +1319,8 @@ inline int kernel_gram(const Kern& kk, int dirX, int dirY, const DevMat& X, cons
     return check(L.dev_sync(st), "sync");
   }
   if (kk.type == K_NONE) return fail(111, "device kernel_gram: unknown kernel");
-  // G = X_p Y_p^T on rocBLAS (X_p = X for row points, X^T for column points)
-  int rc = gemm_rm(dt, !xr, yr, mx, ny, dx, X.data, X.ld, Y.data, Y.ld, 0.0, K.data, K.ld);
-  if (rc) return rc;
-  if (kk.type == K_LINEAR) return check(L.dev_sync(st), "sync");
-  const size_t es = esize(dt);
-  Buf xn(mx * (int64_t)es), yn(ny * (int64_t)es);
-  if (!xn.p || !yn.p) return fail(101, "device kernel_gram: allocation failed");
-  int kind;
+  // every parameter is checked before the GEMM: a refused call leaves K untouched
+  int kind = -1;
   double a = 0, c = 0, q = 1;
   if (kk.type == K_GAUSSIAN) {
     kind = 0;
@@ -1336,7 +1330,7 @@ inline int kernel_gram(const Kern& kk, int dirX, int dirY, const DevMat& X, cons
     q = kk.p[0];
     c = kk.p[1];
     a = kk.p[2];
-  } else {
+  } else if (kk.type == K_MATERN) {
     const double nu = kk.p[0];
     if (nu == 0.5) kind = 3;
     else if (nu == 1.5) kind = 4;
@@ -1344,6 +1338,13 @@ inline int kernel_gram(const Kern& kk, int dirX, int dirY, const DevMat& X, cons
     else return fail(103, "device kernel_gram: Matern nu must be 0.5, 1.5 or 2.5");
     a = 1.0 / kk.p[1];
   }
+  // G = X_p Y_p^T on rocBLAS (X_p = X for row points, X^T for column points)
+  int rc = gemm_rm(dt, !xr, yr, mx, ny, dx, X.data, X.ld, Y.data, Y.ld, 0.0, K.data, K.ld);
+  if (rc) return rc;
+  if (kk.type == K_LINEAR) return check(L.dev_sync(st), "sync");
+  const size_t es = esize(dt);
+  Buf xn(mx * (int64_t)es), yn(ny * (int64_t)es);
+  if (!xn.p || !yn.p) return fail(101, "device kernel_gram: allocation failed");
   if (kind != 1) {
     SLDEV_TRY(L.sqnorms(X.data, dt, mx, dx, xsp, xsd, xn.p, st), "point norms");
     SLDEV_TRY(L.sqnorms(Y.data, dt, ny, dy, ysp, ysd, yn.p, st), "point norms");
