@@ -1,6 +1,6 @@
 """Cross-type dense / sparse / distributed BLAS: ``Gemm``, ``Gemv``, ``Symm``,
 ``Herk``, ``Cholesky`` / ``CholeskySolveAfter`` / ``HPDSolve``, ``Trsm``,
-``TriangularInverse``, explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
+``TriangularInverse``, ``Trtrmm``, ``HPDInverse``, explicit-Q ``QR``, ``Axpy``, views, ``DenseCopy``, shape queries.
 
 Reference: ``base/Gemm.hpp:19-583`` (local dense, sparse x dense in all four
 orientations, ``[VC,*]^T [VC,*] -> [*,*]`` by local GEMM + all-reduce
@@ -644,6 +644,121 @@ def HPDSolve(uplo: str, orient: str, A, B):
     return CholeskySolveAfter(uplo, orient, A, B)
 
 
+def _trtrmm_local(up: str, A: torch.Tensor) -> torch.Tensor:
+    from ..ops import trtrmm as _tm
+    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatchError(f"Trtrmm: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    if _tm.takes(A):
+        # a GPU operand the kernel takes: the native library is mandatory there
+        # (ops/_lib.py), a missing one raises rather than falling back
+        _tm.trtrmm_tri(up, A)
+        return A
+    n = A.shape[0]
+    if n == 0:
+        return A
+    mask = _tri_mask(n, up, A.device)
+    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+    Sh = S.t().conj() if S.is_complex() else S.t()
+    A.copy_(torch.where(mask, Sh @ S if up == "L" else S @ Sh, A))
+    return A
+
+
+def Trtrmm(uplo: str, A):
+    """Overwrite the ``uplo`` triangle of A, which holds a triangular factor,
+    with the same triangle of ``L^H L`` (L) or ``U U^H`` (U): Elemental's
+    ``Trtrmm`` (LAPACK's LAUUM), the last stage of :func:`HPDInverse`.  Only
+    that triangle is read or written; the rest keeps its bits and may hold
+    anything.  Returns A.
+
+    A local f64 matrix on the GPU with unit stride along rows or columns runs
+    the native kernel (``ops/trtrmm.py``, ``trtrmm_tri.hip``): in place,
+    ``n^3 / 3`` flops, no second n x n buffer, no allocation, bit-identical
+    from run to run.  The native library is mandatory there.  Every other
+    local operand (CPU, f32, complex, views with neither unit stride) is one
+    torch product of a masked copy, written back through the triangle mask.
+    A ``[*,*]`` DistMatrix is done on every rank; distributed layouts raise
+    :class:`UnsupportedBaseOperation`."""
+    up = str(uplo).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if _is_dist(A):
+        if A.layout != "STAR_STAR":
+            raise UnsupportedBaseOperation(f"Trtrmm of a {A.layout} matrix (only [*,*] and local)")
+        _trtrmm_local(up, A.local)
+        return A
+    _trtrmm_local(up, _as_tensor(A))
+    return A
+
+
+def _hpd_inverse_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
+    from ..ops import trtrmm as _tm
+    from .exceptions import NLAError
+    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatchError(
+            f"HPDInverse: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    if _tm.takes(A):
+        # the three native stages, in place on the one triangle; a pivot that
+        # is not positive raises in Cholesky, before the other two run
+        _cholesky_local(up, A, info)
+        _triangular_inverse_local(up, "N", A)
+        _trtrmm_local(up, A)
+        return A
+    n = A.shape[0]
+    if n == 0:
+        if info is not None:
+            info.zero_()
+        return A
+    mask = _tri_mask(n, up, A.device)
+    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+    Sh = S.t().conj() if S.is_complex() else S.t()
+    S = S + Sh - torch.diag_embed(S.diagonal())          # the Hermitian matrix that the triangle stores
+    F, linfo = torch.linalg.cholesky_ex(S, upper=up == "U")
+    if info is not None:
+        info.copy_(linfo.reshape(info.shape))
+    else:
+        p = int(linfo.item())
+        if p != 0:
+            raise NLAError(f"HPDInverse: the matrix is not positive definite: pivot {p} (1-based) "
+                           f"is not positive and finite")
+    A.copy_(torch.where(mask, torch.cholesky_inverse(F, upper=up == "U"), A))
+    return A
+
+
+def HPDInverse(uplo: str, A, info=None):
+    """Overwrite the ``uplo`` triangle of the Hermitian positive definite A
+    with the same triangle of ``A^-1``: Elemental's ``HPDInverse`` (reference
+    call site ``ml/BlockADMM.hpp:437``, ``El::Inverse(*Cache[j])``).  Three
+    in-place stages on the one triangle: :func:`Cholesky`,
+    :func:`TriangularInverse`, :func:`Trtrmm` (``A^-1 = X^H X`` with
+    ``X = L^-1``, or ``Y Y^H`` with ``Y = U^-1``).  Only that triangle is read
+    or written; the rest keeps its bits and may hold anything.  Returns A.
+
+    A local f64 matrix on the GPU with unit stride along rows or columns runs
+    native end to end (``chol_tri.hip``, ``trtri_tri.hip``,
+    ``trtrmm_tri.hip``): one buffer, no allocation.  Every other local operand
+    goes through ``torch.linalg.cholesky_ex`` and ``torch.cholesky_inverse``
+    on a masked Hermitian copy, written back through the triangle mask.  A
+    ``[*,*]`` DistMatrix is inverted on every rank; distributed layouts raise
+    :class:`UnsupportedBaseOperation`.
+
+    Failure is :func:`Cholesky`'s: a pivot that is not positive raises
+    :class:`NLAError` naming its 1-based index before the other stages run,
+    unless ``info`` (an int32 one-element tensor on A's device) is given: then
+    the index (0: none) is left there without a host synchronisation and
+    nothing is raised; on a non-zero status the triangle's contents are
+    unspecified."""
+    up = str(uplo).upper()
+    if up not in ("L", "U"):
+        raise ValueError(f"uplo must be L or U (got {uplo})")
+    if _is_dist(A):
+        if A.layout != "STAR_STAR":
+            raise UnsupportedBaseOperation(f"HPDInverse of a {A.layout} matrix (only [*,*] and local)")
+        _hpd_inverse_local(up, A.local, info)
+        return A
+    _hpd_inverse_local(up, _as_tensor(A), info)
+    return A
+
+
 def ExplicitUnitary(A):
     """Overwrite A with the Q factor of its QR (``base/QR.hpp:11-36``): TSQR for
     ``[VC,*]`` (one all-gather of the k x k R factors), Householder locally."""
@@ -731,5 +846,6 @@ def RowDot(X, Y) -> torch.Tensor:
 
 
 __all__ = ["ComputedMatrix", "Gemm", "Gemv", "Symm", "Herk", "Syrk", "MakeSymmetric", "Trsm", "TriangularInverse", "Cholesky", "CholeskySolveAfter", "HPDSolve",
+           "Trtrmm", "HPDInverse",
            "ExplicitUnitary", "QR", "Axpy", "Scale",
            "ColumnView", "RowView", "DenseCopy", "RowDot", "Height", "Width"]

@@ -34,6 +34,7 @@ block parallelism is replaced by GPU-wide parallelism inside each block).
 from __future__ import annotations
 
 import math
+import os
 import time
 
 import torch
@@ -108,6 +109,24 @@ def _gram(Z: torch.Tensor, dt) -> torch.Tensor:
             pass
     Zc = Z.to(dt) if Z.dtype != dt else Z
     return (Zc.t() @ Zc).to(torch.float64)
+
+
+def _block_inverse(C: torch.Tensor, dt) -> torch.Tensor:
+    """``C^-1`` in ``dt`` for the block's cached normal-equation inverse
+    (``El::Inverse(*Cache[j])``, reference ``ml/BlockADMM.hpp:437``); C may be
+    overwritten.  With ``SKH_ADMM_INV=native`` (read at call time) and a C that
+    the one-triangle kernels take (f64 on the GPU), ``base.HPDInverse`` works in
+    place on C's lower triangle (``chol_tri.hip``, ``trtri_tri.hip``,
+    ``trtrmm_tri.hip``: no second or third n x n buffer) and the triangle is
+    mirrored; every other operand, and the default, is the library's Cholesky
+    and ``cholesky_inverse``."""
+    if os.environ.get("SKH_ADMM_INV", "") == "native":
+        from ..base.blas import HPDInverse, MakeSymmetric
+        from ..ops import trtrmm
+        if trtrmm.takes(C):
+            HPDInverse("L", C)
+            return MakeSymmetric("L", C).to(dt)
+    return torch.cholesky_inverse(torch.linalg.cholesky(C)).to(dt)
 
 
 class BlockADMMSolver:
@@ -296,7 +315,7 @@ class BlockADMMSolver:
                 if cache[j] is None:
                     C = _gram(Z, dt)
                     C.diagonal().add_(1.0)
-                    cache[j] = torch.cholesky_inverse(torch.linalg.cholesky(C)).to(dt)
+                    cache[j] = _block_inverse(C, dt)
                 Wb = Wbar[st:st + sj]
                 one_pass = fused and normal_eq.native_ok(Z, kp)
                 # bf16 feature cache: both passes on the matrix cores (the
