@@ -29,15 +29,12 @@
 //                     Panels go in pairs: the first updates only the 64
 //                     columns of the second, the update after the second
 //                     applies both with K = 128, so the trailing matrix is
-//                     read and written once per 128 columns.  The two 128 x K
-//                     panel blocks pass through LDS in slices of 32 columns
-//                     (72 KB, two workgroups per CU: one loads while the
-//                     other multiplies); a 64 x 64 quadrant per wave (16
-//                     accumulator tiles), C loaded into the accumulators and
-//                     the negated P_i as the A operand.  f64 C/D layout:
-//                     col = lane & 15, row = (lane >> 4) + 4 reg.  Diagonal
-//                     tiles load and store only their own triangle (a select
-//                     on row >= col).
+//                     read and written once per 128 columns.  The tile, its
+//                     operand and accumulator layout and the LDS pitch are
+//                     the family's (sl_tri_f64.hpp): C loaded into the
+//                     accumulators, the negated P_i as the A operand, two
+//                     workgroups per CU.  Diagonal tiles load and store only
+//                     their own triangle (a select on row >= col).
 //
 // No workgroup waits on another, there are no atomics and every element is
 // written by exactly one lane per launch: results are bit-identical from run
@@ -51,26 +48,12 @@
 // (7.0 against 5.9 ms at n = 4096).  Open items: wider panel groups, the
 // serial diagonal and panel kernels (33 and 26 us each in a kernel trace) that
 // dominate small n, and the 'U' form's tile stores (32-B runs per row).
-#include "sl_common.hpp"
+#include "sl_tri_f64.hpp"
 #include <math.h>
 
 namespace {
 
-constexpr int NB = 64;          // panel width
-constexpr int T = 128;          // edge of a trailing-update tile
-constexpr int KH = NB / 2;      // panel columns staged in LDS at a time
-constexpr int LP = KH + 4;      // LDS pitch of a staged block (doubles): conflict-free MFMA operand reads
-constexpr int UPD_LDS = 2 * T * LP * (int)sizeof(double);   // 72 KB: two workgroups per CU
-
-typedef __attribute__((ext_vector_type(4))) double f64x4;
-
-// v of lane `lane` (wave-uniform) in every lane
-__device__ __forceinline__ double bcast(double v, int lane) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), lane);
-  return __longlong_as_double((long long)((uint64_t)hi << 32 | lo));
-}
+using namespace sl_tri;         // NB: panel width, T: edge of a trailing-update tile
 
 template <bool LOWER>
 __global__ void __launch_bounds__(64)
@@ -121,6 +104,7 @@ k_chol_panel(double* __restrict__ A, int64_t lda, int64_t n, int64_t j0) {
   double x[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) x[c] = R[c * cs];
+  // not sl_tri::fwd_subst: its pinned row offset was tried here and costs registers (150 -> 162 and 266 -> 268 VGPRs)
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
     double acc = x[c];
@@ -130,40 +114,6 @@ k_chol_panel(double* __restrict__ A, int64_t lda, int64_t n, int64_t j0) {
   }
 #pragma unroll
   for (int c = 0; c < NB; ++c) R[c * cs] = x[c];
-}
-
-// Half `h` (columns [j0 + 32 h, j0 + 32 h + 32) of M) of the panel rows
-// [rb, rb + T) into P[r][k]; rows >= n are zero.  'L' runs along k in memory,
-// 'U' along the rows.
-template <bool LOWER>
-__device__ __forceinline__ void stage_half(const double* __restrict__ A, int64_t lda, int64_t n, int64_t rb,
-                                           int64_t j0, int h, double* __restrict__ P, int tid) {
-  const int64_t rs = LOWER ? lda : 1, cs = LOWER ? 1 : lda;
-#pragma unroll 8
-  for (int idx = tid; idx < T * KH; idx += 256) {
-    const int r = LOWER ? idx / KH : idx & (T - 1), k = LOWER ? idx & (KH - 1) : idx / T;
-    double v = 0.0;
-    if (rb + r < n) v = A[(rb + r) * rs + (j0 + h * KH + k) * cs];
-    P[r * LP + k] = v;
-  }
-}
-
-__device__ __forceinline__ void mma_half(const double* __restrict__ pa, const double* __restrict__ pb,
-                                         f64x4 (&acc)[4][4]) {
-#pragma unroll 4
-  for (int kk = 0; kk < KH / 4; ++kk) {
-    double a[4], b[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      a[m] = -pa[m * 16 * LP + 4 * kk];
-      b[m] = pb[m * 16 * LP + 4 * kk];
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-  }
 }
 
 template <bool LOWER>
@@ -180,6 +130,7 @@ k_chol_update(double* __restrict__ A, int64_t lda, int64_t n, int64_t kc, int ha
   const int64_t rs = LOWER ? lda : 1, cs = LOWER ? 1 : lda;
   const int64_t ri = r0 + (int64_t)I * T, rl = r0 + (int64_t)J * T;
   const bool two = I != J;                // block-uniform
+  // not sl_tri::Quadrant: tried, same registers but another prologue, and n = 16384 then missed its timing limit
   const int wr = wave >> 1, wc = wave & 1;
   // wave-uniform: a quadrant above the diagonal or right of cend stores nothing
   const bool active = (two || wc <= wr) && rl + wc * 64 < cend;
@@ -202,10 +153,11 @@ k_chol_update(double* __restrict__ A, int64_t lda, int64_t n, int64_t kc, int ha
 #pragma unroll 1
   for (int h = 0; h < halves; ++h) {
     if (h) __syncthreads();               // the previous half has been read
-    stage_half<LOWER>(A, lda, n, ri, kc, h, Pi, tid);
-    if (two) stage_half<LOWER>(A, lda, n, rl, kc, h, Pl, tid);
+    // half h of the panel rows [ri, ri + T) and [rl, rl + T): 'L' runs along k in memory, 'U' along the rows
+    stage_slice<LOWER, 8>(A, rs, cs, ri, kc + h * KH, n, Pi, tid);
+    if (two) stage_slice<LOWER, 8>(A, rs, cs, rl, kc + h * KH, n, Pl, tid);
     __syncthreads();
-    if (active) mma_half(pa, pb, acc);
+    if (active) mma_slice<true>(pa, pb, acc);
   }
   if (!active) return;
 #pragma unroll
@@ -221,7 +173,7 @@ k_chol_update(double* __restrict__ A, int64_t lda, int64_t n, int64_t kc, int ha
 
 template <bool LOWER>
 int run(double* A, int64_t n, int64_t lda, int* info, hipStream_t st) {
-  SL_LDS_ATTR((k_chol_update<LOWER>), UPD_LDS);
+  SL_LDS_ATTR((k_chol_update<LOWER>), TILE_LDS);
   // Panels go in pairs, so the trailing matrix is read and written once per
   // 128 columns: the first panel of a pair updates only the second panel's 64
   // columns, and the update after the second applies both (K = 128).
@@ -236,7 +188,7 @@ int run(double* A, int64_t n, int64_t lda, int* info, hipStream_t st) {
     const bool first = (j0 / NB) % 2 == 0;
     const int64_t cend = first ? (r0 + NB < n ? r0 + NB : n) : n;
     const unsigned ntr = (unsigned)((rem + T - 1) / T), ntc = (unsigned)((cend - r0 + T - 1) / T);
-    k_chol_update<LOWER><<<dim3(ntc, ntr), 256, UPD_LDS, st>>>(A, lda, n, first ? j0 : j0 - NB, first ? 2 : 4, r0, cend);
+    k_chol_update<LOWER><<<dim3(ntc, ntr), 256, TILE_LDS, st>>>(A, lda, n, first ? j0 : j0 - NB, first ? 2 : 4, r0, cend);
     SL_LAUNCH_CHECK();
   }
   return SL_OK;

@@ -36,13 +36,11 @@
 //   wide (t > 8)   2 ceil(n / 64) - 1 launches.  k_trsm_wdiag: one lane per
 //                  right-hand side keeps its 64 unknowns in registers, M_jj in
 //                  LDS (broadcast reads), one 64-lane workgroup per 64
-//                  right-hand sides.  k_trsm_wupdate: 128 x 128 tiles of (rows x
-//                  right-hand sides) on v_mfma_f64_16x16x4_f64, K = 64 in two
-//                  slices of 32 through LDS (72 KB, two workgroups per CU),
-//                  operand layout, accumulator layout (col = lane & 15, row =
-//                  (lane >> 4) + 4 reg) and the conflict-free pitch of 36 as in
-//                  k_chol_update, C loaded into the accumulators.  The MFMA
-//                  column index (lane & 15) is put on B's unit-stride
+//                  right-hand sides (the family's substitution,
+//                  sl_tri_f64.hpp).  k_trsm_wupdate: the family's 128 x 128
+//                  tile of (rows x right-hand sides), K = 64 in two slices,
+//                  two workgroups per CU, C loaded into the accumulators.  The
+//                  MFMA column index (lane & 15) is put on B's unit-stride
 //                  dimension: (-M) X for side L, (-X^T) M^T for side R.
 //
 // No workgroup waits on another, there are no atomics and every element of B
@@ -52,7 +50,7 @@
 // is 0 bytes per lane in all 16 instantiations.  k_trsm_thin 54-58 VGPRs,
 // k_trsm_wdiag 255-256, k_trsm_wupdate 242-250 (two workgroups per CU).
 // k_trsm_wdiag kept 15 KB of scratch per lane until each row's LDS offset was
-// tied to the previous unknown (see there); k_trsm_wupdate spilled 12-28 bytes
+// tied to the previous unknown (see fwd_subst); k_trsm_wupdate spilled 12-28 bytes
 // with its staging loops unrolled by 8 and does not with 4.
 //
 // Measured (one MI355X, side L, uplo L, median of 5, ms; native / rocBLAS
@@ -75,19 +73,13 @@
 // Not measured: the K = 128 pairing of two diagonal blocks per pass over B,
 // side R and uplo U timings, a kernel trace that splits a launch into gap,
 // update and solve, and t between 9 and 255.
-#include "sl_common.hpp"
+#include "sl_tri_f64.hpp"
 
 namespace {
 
-constexpr int NB = 64;          // diagonal block width
-constexpr int T = 128;          // edge of a wide-update tile
+using namespace sl_tri;         // NB: diagonal block width, T: edge of a wide-update tile
 constexpr int THIN = 8;         // t <= THIN takes the thin regime
-constexpr int KH = NB / 2;      // block columns staged in LDS at a time (wide update)
-constexpr int LP = KH + 4;      // LDS pitch of a staged slice (doubles): conflict-free MFMA operand reads
-constexpr int UPD_LDS = 2 * T * LP * (int)sizeof(double);   // 72 KB: two workgroups per CU
 constexpr int TP = NB + 1;      // LDS pitch of a thin 64 x 64 piece: lane = row reads are conflict-free
-
-typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 // the logical views
 struct View {
@@ -95,14 +87,6 @@ struct View {
   double* B;                    // Bv[i][r] = B[i * brs + r * bcs]
   int64_t ars, acs, brs, bcs, n, t;
 };
-
-// v of lane `lane` (wave-uniform) in every lane
-__device__ __forceinline__ double bcast(double v, int lane) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), lane);
-  return __longlong_as_double((long long)((uint64_t)hi << 32 | lo));
-}
 
 // ---------------------------------------------------------------- thin
 // Rows [r0 + 64 b, + 64) for workgroup b: B -= M[rows, r0 - 64 : r0] X (r0 > 0),
@@ -212,63 +196,10 @@ k_trsm_wdiag(const View v, const int64_t j0, const int w) {
   double x[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) x[c] = c < w ? R[c * v.brs] : 0.0;
-#pragma unroll
-  for (int c = 0; c < NB; ++c) {
-    double acc = x[c];
-    // Row c's LDS offset is made to depend on x[c - 1]: otherwise all 2080 reads
-    // of Ld are hoisted to the top and spilled (15 KB of scratch per lane).
-    int off = c * NB;
-    if (c) asm volatile("" : "+v"(off) : "v"(x[c - 1]));
-    const double* row = Ld + off;
-#pragma unroll
-    for (int k = 0; k < c; ++k) acc = fma(-x[k], row[k], acc);
-    x[c] = UNIT ? acc : acc / row[c];
-  }
+  fwd_subst<UNIT, NB>(Ld, x);
 #pragma unroll
   for (int c = 0; c < NB; ++c)
     if (c < w) R[c * v.brs] = x[c];
-}
-
-// Slice h (columns [j0 + 32 h, + 32) of M) of rows [rb, rb + T) into P[row][k]; rows >= n are zero.
-template <bool AROW>
-__device__ __forceinline__ void stage_m(const View& v, int64_t rb, int64_t j0, int h, double* __restrict__ P, int tid) {
-#pragma unroll 4
-  for (int idx = tid; idx < T * KH; idx += 256) {
-    const int r = AROW ? idx / KH : idx & (T - 1), k = AROW ? idx & (KH - 1) : idx / T;
-    double m = 0.0;
-    if (rb + r < v.n) m = v.M[(rb + r) * v.ars + (j0 + h * KH + k) * v.acs];
-    P[r * LP + k] = m;
-  }
-}
-
-// Slice h of X_j (rows [j0 + 32 h, + 32) of Bv) for right-hand sides [cb, cb + T) into P[rhs][k]; rhs >= t are zero.
-template <bool BROW>
-__device__ __forceinline__ void stage_x(const View& v, int64_t cb, int64_t j0, int h, double* __restrict__ P, int tid) {
-#pragma unroll 4
-  for (int idx = tid; idx < T * KH; idx += 256) {
-    const int r = BROW ? idx & (T - 1) : idx / KH, k = BROW ? idx / T : idx & (KH - 1);
-    double x = 0.0;
-    if (cb + r < v.t) x = v.B[(j0 + h * KH + k) * v.brs + (cb + r) * v.bcs];
-    P[r * LP + k] = x;
-  }
-}
-
-__device__ __forceinline__ void mma_half(const double* __restrict__ pa, const double* __restrict__ pb,
-                                         f64x4 (&acc)[4][4]) {
-#pragma unroll 4
-  for (int kk = 0; kk < KH / 4; ++kk) {
-    double a[4], b[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      a[m] = -pa[m * 16 * LP + 4 * kk];
-      b[m] = pb[m * 16 * LP + 4 * kk];
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-  }
 }
 
 // Bv[i, r] -= M[i, j0 : j0 + 64] X_j[:, r] over rows i >= r0, a T x T tile of (rows x rhs) per workgroup.
@@ -282,15 +213,14 @@ k_trsm_wupdate(const View v, const int64_t j0, const int64_t r0) {
   double* Xs = Ms + T * LP;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t ri = r0 + (int64_t)blockIdx.y * T, cb = (int64_t)blockIdx.x * T;
-  const int wp = wave >> 1, wq = wave & 1;
-  const int fr = lane & 15, fq = lane >> 4;
+  const Quadrant q(lane, wave);
   const int64_t plim = BROW ? v.n : v.t, qlim = BROW ? v.t : v.n;
   const int64_t ps = BROW ? v.brs : v.bcs, qs = BROW ? v.bcs : v.brs;
-  const int64_t gp0 = (BROW ? ri : cb) + wp * 64 + fq, gq0 = (BROW ? cb : ri) + wq * 64 + fr;
+  const int64_t gp0 = (BROW ? ri : cb) + q.wp * 64 + q.fq, gq0 = (BROW ? cb : ri) + q.wq * 64 + q.fr;
   // wave-uniform: a quadrant past the last row or the last right-hand side stores nothing
-  const bool active = gp0 - fq < plim && gq0 - fr < qlim;
-  const double* pa = (BROW ? Ms : Xs) + (wp * 64 + fr) * LP + fq;
-  const double* pb = (BROW ? Xs : Ms) + (wq * 64 + fr) * LP + fq;
+  const bool active = gp0 - q.fq < plim && gq0 - q.fr < qlim;
+  const double* pa = q.operand(BROW ? Ms : Xs, q.wp);
+  const double* pb = q.operand(BROW ? Xs : Ms, q.wq);
   f64x4 acc[4][4];
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
@@ -306,10 +236,12 @@ k_trsm_wupdate(const View v, const int64_t j0, const int64_t r0) {
 #pragma unroll 1
   for (int h = 0; h < NB / KH; ++h) {
     if (h) __syncthreads();               // the previous slice has been read
-    stage_m<AROW>(v, ri, j0, h, Ms, tid);
-    stage_x<BROW>(v, cb, j0, h, Xs, tid);
+    // slice h of M[ri : ri + T, j0 : j0 + 64] and of X_j for the right-hand sides [cb, cb + T), as P[row or rhs][k];
+    // 4 loads in flight: 8 spill
+    stage_slice<AROW, 4>(v.M, v.ars, v.acs, ri, j0 + h * KH, v.n, Ms, tid);
+    stage_slice<!BROW, 4>(v.B, v.bcs, v.brs, cb, j0 + h * KH, v.t, Xs, tid);
     __syncthreads();
-    if (active) mma_half(pa, pb, acc);
+    if (active) mma_slice<true>(pa, pb, acc);
   }
   if (!active) return;
 #pragma unroll
@@ -334,7 +266,7 @@ int run(const View& v, hipStream_t st) {
     }
     return SL_OK;
   }
-  SL_LDS_ATTR((k_trsm_wupdate<AROW, BROW>), UPD_LDS);
+  SL_LDS_ATTR((k_trsm_wupdate<AROW, BROW>), TILE_LDS);
   const unsigned ntc = (unsigned)((t + T - 1) / T);
   for (int64_t j0 = 0; j0 < n; j0 += NB) {
     const int w = (int)(n - j0 < NB ? n - j0 : NB);
@@ -342,7 +274,7 @@ int run(const View& v, hipStream_t st) {
     SL_LAUNCH_CHECK();
     const int64_t r0 = j0 + w, rem = n - r0;
     if (rem <= 0) break;
-    k_trsm_wupdate<AROW, BROW><<<dim3(ntc, (unsigned)((rem + T - 1) / T)), 256, UPD_LDS, st>>>(v, j0, r0);
+    k_trsm_wupdate<AROW, BROW><<<dim3(ntc, (unsigned)((rem + T - 1) / T)), 256, TILE_LDS, st>>>(v, j0, r0);
     SL_LAUNCH_CHECK();
   }
   return SL_OK;

@@ -26,13 +26,11 @@
 //                      (no inverse of a block is multiplied in): the four waves
 //                      stage A11 in LDS in one pass of loads, then one lane per
 //                      column keeps its 64 unknowns in registers (broadcast reads
-//                      of A11), one workgroup per 64 columns, as k_trsm_wdiag.
+//                      of A11), one workgroup per 64 columns: the family's
+//                      substitution (sl_tri_f64.hpp).
 //   2. k_trtri_update  A20 -= A21 A10 with the new A10 and the still original
-//                      A21: 128 x 128 tiles on v_mfma_f64_16x16x4_f64, K = 64 in
-//                      two slices of 32 through LDS (72 KB, two workgroups per
-//                      CU), operand layout, accumulator layout (col = lane & 15,
-//                      row = (lane >> 4) + 4 reg) and the conflict-free pitch of
-//                      36 as in k_chol_update / k_trsm_wupdate.  Workgroup 0 of
+//                      A21: the family's 128 x 128 tile, K = 64 in two slices,
+//                      two workgroups per CU.  Workgroup 0 of
 //                      this launch takes no tile: it computes X11 = A11^-1 I
 //                      with the same substitution (the identity is generated,
 //                      not loaded; only the triangle of X11 is stored; with diag
@@ -88,15 +86,11 @@
 // Not measured: the K = 128 pairing of two diagonal blocks per pass over A20,
 // folding launch 3 into a neighbour, uplo L, diag U and column-major timings,
 // n between 5000 and 16384, more staging loads in flight in the update tile.
-#include "sl_common.hpp"
+#include "sl_tri_f64.hpp"
 
 namespace {
 
-constexpr int NB = 64;          // diagonal block width
-constexpr int T = 128;          // edge of an update tile
-constexpr int KH = NB / 2;      // block columns staged in LDS at a time (update)
-constexpr int LP = KH + 4;      // LDS pitch of a staged slice (doubles): conflict-free MFMA operand reads
-constexpr int UPD_LDS = 2 * T * LP * (int)sizeof(double);                 // 72 KB: two workgroups per CU
+using namespace sl_tri;         // NB: diagonal block width, T: edge of an update tile
 constexpr int CH = 16;          // global loads a lane keeps in flight while staging
 constexpr int DP = NB + 2;      // LDS pitch of a diagonal block: rows i .. i + 3 fall in different banks, 16-B aligned rows
 constexpr int AP = NB + 1;      // LDS pitch of a staged 64 x 64 piece of A21: lane = row reads are conflict-free
@@ -105,9 +99,7 @@ static_assert(NB * NB == 256 * CH, "the 256-thread kernels stage a 64 x 64 block
 // Rows of pitch DP that workgroup 0 of the update may read in the tiles' LDS: the 64 of A11 and, into registers
 // that nothing uses, on to row 3 + 4 (15 + 15) (see ident_step).
 constexpr int IDENT_ROWS = 3 + 4 * 2 * (NB / 4 - 1) + 1;
-static_assert(IDENT_ROWS * DP * (int)sizeof(double) <= UPD_LDS, "workgroup 0 of the update reads inside the tiles' LDS");
-
-typedef __attribute__((ext_vector_type(4))) double f64x4;
+static_assert(IDENT_ROWS * DP * (int)sizeof(double) <= TILE_LDS, "workgroup 0 of the update reads inside the tiles' LDS");
 
 // the logical lower-triangular view L[i][c] = M[i * rs + c * cs], |cs| = 1
 struct View {
@@ -150,11 +142,11 @@ __device__ __forceinline__ void col_solve(const View& v, const double* Ld, int64
 #pragma unroll
     for (int c = 0; c < NB; ++c) x[c] = c < w ? R[c * v.rs] : 0.0;
   }
+  // sl_tri::fwd_subst<UNIT, DP> written out: the call was tried, same registers but another branch order, and
+  // n = 16384 then missed its timing limit in one of two runs
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
     double acc = x[c];
-    // Row c's LDS offset is made to depend on x[c - 1]: otherwise all 2080 reads
-    // of Ld are hoisted to the top and spilled (see k_trsm_wdiag).
     int off = c * DP;
     if (c) asm volatile("" : "+v"(off) : "v"(x[c - 1]));
     const double* row = Ld + off;
@@ -239,46 +231,6 @@ k_trtri_row(const View v, const int64_t j0, const int w) {
 }
 
 // ---------------------------------------------------------------- launch 2
-// Slice h (columns [j0 + 32 h, + 32) of L) of rows [rb, rb + T) into P[row][k]; rows >= n are zero.
-__device__ __forceinline__ void stage_m(const View& v, int64_t rb, int64_t j0, int h, double* __restrict__ P, int tid) {
-#pragma unroll 4
-  for (int idx = tid; idx < T * KH; idx += 256) {
-    const int r = idx / KH, k = idx & (KH - 1);
-    double m = 0.0;
-    if (rb + r < v.n) m = v.M[(rb + r) * v.rs + (j0 + h * KH + k) * v.cs];
-    P[r * LP + k] = m;
-  }
-}
-
-// Slice h of A10 (rows [j0 + 32 h, + 32) of L) for columns [cb, cb + T) into P[column][k]; columns >= j0 are zero.
-__device__ __forceinline__ void stage_x(const View& v, int64_t cb, int64_t j0, int h, double* __restrict__ P, int tid) {
-#pragma unroll 4
-  for (int idx = tid; idx < T * KH; idx += 256) {
-    const int r = idx & (T - 1), k = idx / T;
-    double x = 0.0;
-    if (cb + r < j0) x = v.M[(j0 + h * KH + k) * v.rs + (cb + r) * v.cs];
-    P[r * LP + k] = x;
-  }
-}
-
-__device__ __forceinline__ void mma_half(const double* __restrict__ pa, const double* __restrict__ pb,
-                                         f64x4 (&acc)[4][4]) {
-#pragma unroll 4
-  for (int kk = 0; kk < KH / 4; ++kk) {
-    double a[4], b[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      a[m] = -pa[m * 16 * LP + 4 * kk];
-      b[m] = pb[m * 16 * LP + 4 * kk];
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-  }
-}
-
 // Workgroup 0: X11 = A11^-1 I over A11 (w x w at j0).  Workgroup 1 + t: tile t of A20[i, r] -= A21[i, :] A10[:, r],
 // rows i >= j0 + 64, columns r < j0, `ntc` tiles across; there are tiles only when w = 64.  The MFMA row index
 // (lane >> 4, registers) is the row and the column index (lane & 15) the column, which runs along memory.
@@ -298,13 +250,12 @@ k_trtri_update(const View v, const int64_t j0, const int w, const unsigned ntc) 
   const unsigned tile = blockIdx.x - 1;
   const int64_t r0 = j0 + NB;
   const int64_t ri = r0 + (int64_t)(tile / ntc) * T, cb = (int64_t)(tile % ntc) * T;
-  const int wp = wave >> 1, wq = wave & 1;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int64_t gp0 = ri + wp * 64 + fq, gq0 = cb + wq * 64 + fr;
+  const Quadrant q(lane, wave);
+  const int64_t gp0 = ri + q.wp * 64 + q.fq, gq0 = cb + q.wq * 64 + q.fr;
   // wave-uniform: a quadrant past the last row or the last column stores nothing
-  const bool active = gp0 - fq < v.n && gq0 - fr < j0;
-  const double* pa = Ms + (wp * 64 + fr) * LP + fq;
-  const double* pb = Xs + (wq * 64 + fr) * LP + fq;
+  const bool active = gp0 - q.fq < v.n && gq0 - q.fr < j0;
+  const double* pa = q.operand(Ms, q.wp);
+  const double* pb = q.operand(Xs, q.wq);
   f64x4 acc[4][4];
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
@@ -320,10 +271,12 @@ k_trtri_update(const View v, const int64_t j0, const int w, const unsigned ntc) 
 #pragma unroll 1
   for (int h = 0; h < NB / KH; ++h) {
     if (h) __syncthreads();               // the previous slice has been read
-    stage_m(v, ri, j0, h, Ms, tid);
-    stage_x(v, cb, j0, h, Xs, tid);
+    // slice h of A21 (rows [ri, ri + T), columns [j0 + 32 h, + 32) of L) as P[row][k], and of A10 (rows [j0 + 32 h,
+    // + 32) of L) for the columns [cb, cb + T) as P[column][k]; columns >= j0 are zero
+    stage_slice<true, 4>(v.M, v.rs, v.cs, ri, j0 + h * KH, v.n, Ms, tid);
+    stage_slice<false, 4>(v.M, v.cs, v.rs, cb, j0 + h * KH, j0, Xs, tid);
     __syncthreads();
-    if (active) mma_half(pa, pb, acc);
+    if (active) mma_slice<true>(pa, pb, acc);
   }
   if (!active) return;
 #pragma unroll
@@ -348,7 +301,7 @@ __device__ __forceinline__ void panel_part(const double* Xs, const double* As, d
   for (int c = JB; c < NB; ++c) a[c - JB] = As[lane * AP + c];
 #pragma unroll
   for (int j = JB; j < JB + 16; ++j) {
-    // Column j's LDS offset is made to depend on the previous entry, as in col_solve.
+    // Column j's LDS offset is made to depend on the previous entry, as in fwd_subst.
     int off = j;
     if (j > JB) asm volatile("" : "+v"(off) : "v"(a[j - 1 - JB]));
     const double* col = Xs + off;
@@ -401,7 +354,7 @@ k_trtri_panel(const View v, const int64_t j0) {
 template <bool UNIT>
 int run(const View& v, hipStream_t st) {
   const int64_t n = v.n;
-  SL_LDS_ATTR((k_trtri_update<UNIT>), UPD_LDS);
+  SL_LDS_ATTR((k_trtri_update<UNIT>), TILE_LDS);
   SL_LDS_ATTR((k_trtri_panel<UNIT>), PANEL_LDS);
   for (int64_t j0 = 0; j0 < n; j0 += NB) {
     const int w = (int)(n - j0 < NB ? n - j0 : NB);
@@ -411,7 +364,7 @@ int run(const View& v, hipStream_t st) {
     }
     const int64_t rem = n - j0 - w;       // rem > 0 only below a full block
     const unsigned ntc = rem > 0 ? (unsigned)((j0 + T - 1) / T) : 0u, ntr = (unsigned)((rem + T - 1) / T);
-    k_trtri_update<UNIT><<<1u + ntc * ntr, 256, UPD_LDS, st>>>(v, j0, w, ntc ? ntc : 1u);
+    k_trtri_update<UNIT><<<1u + ntc * ntr, 256, TILE_LDS, st>>>(v, j0, w, ntc ? ntc : 1u);
     SL_LAUNCH_CHECK();
     if (rem <= 0) break;
     k_trtri_panel<UNIT><<<(unsigned)((rem + NB - 1) / NB), 256, PANEL_LDS, st>>>(v, j0);

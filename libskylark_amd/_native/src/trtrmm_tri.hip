@@ -42,16 +42,15 @@
 // launch writes (its own, the slab, or L[r][r]), and a workgroup's own global reads are complete (staged through
 // LDS behind barriers) before its stores.  2 nblk - 1 launches for n > 0, one for n <= 128.
 //
-// The tile is that of k_trtri_update: 128 x 128 on v_mfma_f64_16x16x4_f64, four waves each owning a 64 x 64 quadrant,
-// K in slices of 32 through LDS (two operand slices of pitch 36, 72 KB), the same operand and accumulator layout
-// (col = lane & 15, row = (lane >> 4) + 4 reg).  K positions that fall outside the triangle (the diagonal blocks of a
+// The tile is the family's (sl_tri_f64.hpp: 128 x 128, K in slices of 32 through LDS, operand and accumulator
+// layout); the staging is this file's own.  K positions that fall outside the triangle (the diagonal blocks of a
 // slab: k < x) or outside the matrix are staged as explicit zeros; a loaded value is never multiplied by zero.
 // Diagonal output tiles load and store their triangle only, and a wave whose quadrant lies in the other triangle or
 // outside the matrix issues no MFMA.  All 32 loads of a thread's staging pass are issued before the first is used,
 // and the loads of slice h + 1 are in flight while slice h is multiplied.  Tiles whose blocks lie wholly inside the
 // matrix and off the diagonal (all but O(nblk) of a launch) stage and store without tests; the others load without
 // branches (see load_slice).
-// Two things differ from k_trtri_update, both decided by the compile log, not by a measurement against it.  (1) One
+// Two things differ from the other kernels of the family, both decided by the compile log, not by a measurement against it.  (1) One
 // workgroup per CU, not two: the 64 registers of the slice in flight next to the 128 accumulator registers do not
 // fit 256 registers per lane (__launch_bounds__(256, 2): 233 / 264 registers spilled, 608 / 732 bytes of scratch per
 // lane; still 151 / 200 spilled with no slice in flight), and they fit 512.  (2) The staging index map of the
@@ -84,18 +83,17 @@
 // Not measured: two workgroups per CU with fewer loads in flight, 64 x 64 tiles or a split of K for the launches
 // that do not fill the chip, a separate workgroup shape for the two-pass tile, NB = 256 slabs (half the launches),
 // column-major timings, n beyond 8192, sizes that are no multiple of 128.
-#include "sl_common.hpp"
+#include "sl_tri_f64.hpp"
 
 namespace {
 
-constexpr int T = 128;          // block width of the schedule and edge of a tile
-constexpr int KH = 32;          // slab rows staged in LDS at a time
-constexpr int LP = KH + 4;      // LDS pitch of a staged slice (doubles): conflict-free MFMA operand reads
-constexpr int TILE_LDS = 2 * T * LP * (int)sizeof(double);                // 72 KB
+using sl_tri::T;                // block width of the schedule and edge of a tile
+using sl_tri::KH;               // slab rows staged in LDS at a time
+using sl_tri::LP;
+using sl_tri::TILE_LDS;
+using sl_tri::f64x4;
 constexpr int CH = T * KH / 256;                                          // loads per thread and operand slice
 constexpr int64_t MAX_PITCH = (int64_t)1 << 22;   // byte offsets inside a block fit 32 bits: (127 pitch + 127) 8 < 2^32
-
-typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 struct Mat {
   double* A;
@@ -159,24 +157,6 @@ __device__ __forceinline__ void store_slice(double* __restrict__ P, int tid, con
   for (int u = 0; u < CH; ++u) P[px<TV>(tid, u) * LP + pk<TV>(tid, u)] = t[u];
 }
 
-__device__ __forceinline__ void mma_slice(const double* __restrict__ pa, const double* __restrict__ pb,
-                                          f64x4 (&acc)[4][4]) {
-#pragma unroll 4
-  for (int kk = 0; kk < KH / 4; ++kk) {
-    double a[4], b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      a[q] = pa[q * 16 * LP + 4 * kk];
-      b[q] = pb[q * 16 * LP + 4 * kk];
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-  }
-}
-
 // acc += L[R][BM]^T L[R][BN] over the T rows of slab R (BM / BN: the blocks of the MFMA's row / column operand).
 template <bool TV, bool GUARD>
 __device__ __forceinline__ void slab_pass(const Mat& m, int64_t R, int64_t BM, int64_t BN, double* Ms, double* Xs,
@@ -195,7 +175,7 @@ __device__ __forceinline__ void slab_pass(const Mat& m, int64_t R, int64_t BM, i
       load_slice<TV, GUARD>(m, R * T, BM * T, (h + 1) * KH, R == BM, tid, voff, ta);
       load_slice<TV, GUARD>(m, R * T, BN * T, (h + 1) * KH, R == BN, tid, voff, tb);
     }
-    if (active) mma_slice(pa, pb, acc);
+    if (active) sl_tri::mma_slice<false>(pa, pb, acc);
   }
 }
 

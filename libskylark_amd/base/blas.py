@@ -355,6 +355,50 @@ def _tri_update(C: torch.Tensor, uplo: str, P: torch.Tensor, beta) -> torch.Tens
     return C
 
 
+def _flag(value, name: str, allowed: str) -> str:
+    from ..ops import _tri
+    return _tri.flag(value, name, allowed)
+
+
+def _masked(A: torch.Tensor, uplo: str):
+    """``(mask, S)``: the mask of the ``uplo`` triangle and A with zeros outside it."""
+    mask = _tri_mask(A.shape[0], uplo, A.device)
+    return mask, torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+
+
+def _dense_square(name: str, A) -> None:
+    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
+        raise DimensionMismatchError(f"{name}: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+
+
+def _pivot_status(name: str, linfo: torch.Tensor, info) -> None:
+    """``cholesky_ex``'s status into ``info``, or raised when there is none."""
+    from .exceptions import NLAError
+    if info is not None:
+        info.copy_(linfo.reshape(info.shape))
+        return
+    p = int(linfo.item())
+    if p != 0:
+        raise NLAError(f"{name}: the matrix is not positive definite: pivot {p} (1-based) "
+                       f"is not positive and finite")
+
+
+def _tri_in_place(name: str, local, uplo, A, *rest, diag=None):
+    """The frame of the in-place one-triangle operations: the flags, a
+    DistMatrix only as ``[*,*]`` (done on every rank), ``local(uplo[, diag],
+    tensor, *rest)`` on the local matrix; returns A."""
+    flags = (_flag(uplo, "uplo", "LU"),)
+    if diag is not None:
+        flags += (_flag(diag, "diag", "NU"),)
+    if _is_dist(A):
+        if A.layout != "STAR_STAR":
+            raise UnsupportedBaseOperation(f"{name} of a {A.layout} matrix (only [*,*] and local)")
+        local(*flags, A.local, *rest)
+    else:
+        local(*flags, _as_tensor(A), *rest)
+    return A
+
+
 def _herk_local(uplo: str, trans: bool, alpha, A: torch.Tensor, beta, C: torch.Tensor | None) -> torch.Tensor:
     if A.layout != torch.strided:
         A = A.to_dense()
@@ -398,11 +442,7 @@ def Herk(uplo: str, orient: str, alpha, A, beta=0.0, C=None):
     product in the operand's precision written through a triangle mask.
     ``[VC,*]`` A with orient T: local Herk + one all-reduce of the s x s
     block, replicated result; other distributed layouts are gathered."""
-    up, o = str(uplo).upper(), str(orient).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if o not in ("N", "T", "C"):
-        raise ValueError(f"orientation must be N, T or C (got {orient})")
+    up, o = _flag(uplo, "uplo", "LU"), _flag(orient, "orientation", "NTC")
     Ct = C.local if _is_dist(C) else C
     if _is_dist(A):
         from ..parallel.distmatrix import is_row_dist
@@ -427,9 +467,7 @@ Syrk = Herk
 
 def MakeSymmetric(uplo: str, C):
     """Copy the stored ``uplo`` triangle of C over the other one, in place."""
-    up = str(uplo).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
+    up = _flag(uplo, "uplo", "LU")
     Ct = C.local if _is_dist(C) else C
     other = Ct.t().conj() if Ct.is_complex() else Ct.t()
     Ct.copy_(torch.where(_tri_mask(Ct.shape[0], up, Ct.device), Ct, other))
@@ -488,9 +526,7 @@ def Trsm(side: str, uplo: str, orient: str, diag: str, alpha, A, B):
 
 def _triangular_inverse_local(up: str, dg: str, A: torch.Tensor) -> torch.Tensor:
     from ..ops import trtri as _ti
-    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
-        raise DimensionMismatchError(
-            f"TriangularInverse: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    _dense_square("TriangularInverse", A)
     if _ti.takes(A):
         # a GPU operand the kernel takes: the native library is mandatory there
         # (ops/_lib.py), a missing one raises rather than falling back
@@ -499,9 +535,8 @@ def _triangular_inverse_local(up: str, dg: str, A: torch.Tensor) -> torch.Tensor
     n = A.shape[0]
     if n == 0:
         return A
-    mask = _tri_mask(n, up, A.device)
+    mask, S = _masked(A, up)
     eye = torch.eye(n, dtype=A.dtype, device=A.device)
-    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
     if dg == "U":
         mask = mask & ~eye.bool()
         S = torch.where(mask, S, eye)
@@ -527,44 +562,21 @@ def TriangularInverse(uplo: str, diag: str, A):
     against the identity, written back through the triangle mask.  A ``[*,*]``
     DistMatrix is inverted on every rank; distributed layouts raise
     :class:`UnsupportedBaseOperation`."""
-    up, dg = str(uplo).upper(), str(diag).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if dg not in ("N", "U"):
-        raise ValueError(f"diag must be N or U (got {diag})")
-    if _is_dist(A):
-        if A.layout != "STAR_STAR":
-            raise UnsupportedBaseOperation(f"TriangularInverse of a {A.layout} matrix (only [*,*] and local)")
-        _triangular_inverse_local(up, dg, A.local)
-        return A
-    _triangular_inverse_local(up, dg, _as_tensor(A))
-    return A
+    return _tri_in_place("TriangularInverse", _triangular_inverse_local, uplo, A, diag=diag)
 
 
 def _cholesky_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
-    from ..ops import cholesky as _ch
-    from .exceptions import NLAError
-    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
-        raise DimensionMismatchError(f"Cholesky: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
-    An, un = A, up
-    if A.shape[1] > 1 and A.stride(1) != 1 and A.stride(0) == 1:
-        # a column-major A is the row-major transpose with the other triangle stored
-        An, un = A.t(), ("U" if up == "L" else "L")
+    from ..ops import _tri, cholesky as _ch
+    _dense_square("Cholesky", A)
+    An, un = _tri.row_major(A, (up, "LU"))
     if _ch.takes(An):
         # a GPU operand the kernel takes: the native library is mandatory there
         # (ops/_lib.py), a missing one raises rather than falling back
         _ch.chol_tri(An, un, info)
         return A
-    S = torch.where(_tri_mask(A.shape[0], up, A.device), A, torch.zeros((), dtype=A.dtype, device=A.device))
-    F, linfo = torch.linalg.cholesky_ex(S, upper=up == "U")
+    F, linfo = torch.linalg.cholesky_ex(_masked(A, up)[1], upper=up == "U")
     _tri_update(A, up, F, 0.0)
-    if info is not None:
-        info.copy_(linfo.reshape(info.shape))
-    else:
-        p = int(linfo.item())
-        if p != 0:
-            raise NLAError(f"Cholesky: the matrix is not positive definite: pivot {p} (1-based) "
-                           f"is not positive and finite")
+    _pivot_status("Cholesky", linfo, info)
     return A
 
 
@@ -587,16 +599,7 @@ def Cholesky(uplo: str, A, info=None):
     index, unless ``info`` (an int32 one-element tensor on A's device) is
     given: then the index (0: none) is left there without a host
     synchronisation and nothing is raised."""
-    up = str(uplo).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if _is_dist(A):
-        if A.layout != "STAR_STAR":
-            raise UnsupportedBaseOperation(f"Cholesky of a {A.layout} matrix (only [*,*] and local)")
-        _cholesky_local(up, A.local, info)
-        return A
-    _cholesky_local(up, _as_tensor(A), info)
-    return A
+    return _tri_in_place("Cholesky", _cholesky_local, uplo, A, info)
 
 
 def CholeskySolveAfter(uplo: str, orient: str, F, B):
@@ -609,11 +612,7 @@ def CholeskySolveAfter(uplo: str, orient: str, F, B):
     (``tests/test_gpu_chol.py``), so F is never masked into a temporary.
     ``orient`` N, or T / C for real data (A is symmetric); B local or a
     DistMatrix with replicated rows.  Returns B."""
-    up, o = str(uplo).upper(), str(orient).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if o not in ("N", "T", "C"):
-        raise ValueError(f"orientation must be N, T or C (got {orient})")
+    up, o = _flag(uplo, "uplo", "LU"), _flag(orient, "orientation", "NTC")
     Fl = F.local if _is_dist(F) else _as_tensor(F)
     if _is_dist(F) and F.layout != "STAR_STAR":
         raise UnsupportedBaseOperation(f"CholeskySolveAfter with a {F.layout} factor (only [*,*] and local)")
@@ -646,8 +645,7 @@ def HPDSolve(uplo: str, orient: str, A, B):
 
 def _trtrmm_local(up: str, A: torch.Tensor) -> torch.Tensor:
     from ..ops import trtrmm as _tm
-    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
-        raise DimensionMismatchError(f"Trtrmm: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    _dense_square("Trtrmm", A)
     if _tm.takes(A):
         # a GPU operand the kernel takes: the native library is mandatory there
         # (ops/_lib.py), a missing one raises rather than falling back
@@ -656,8 +654,7 @@ def _trtrmm_local(up: str, A: torch.Tensor) -> torch.Tensor:
     n = A.shape[0]
     if n == 0:
         return A
-    mask = _tri_mask(n, up, A.device)
-    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+    mask, S = _masked(A, up)
     Sh = S.t().conj() if S.is_complex() else S.t()
     A.copy_(torch.where(mask, Sh @ S if up == "L" else S @ Sh, A))
     return A
@@ -678,24 +675,12 @@ def Trtrmm(uplo: str, A):
     torch product of a masked copy, written back through the triangle mask.
     A ``[*,*]`` DistMatrix is done on every rank; distributed layouts raise
     :class:`UnsupportedBaseOperation`."""
-    up = str(uplo).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if _is_dist(A):
-        if A.layout != "STAR_STAR":
-            raise UnsupportedBaseOperation(f"Trtrmm of a {A.layout} matrix (only [*,*] and local)")
-        _trtrmm_local(up, A.local)
-        return A
-    _trtrmm_local(up, _as_tensor(A))
-    return A
+    return _tri_in_place("Trtrmm", _trtrmm_local, uplo, A)
 
 
 def _hpd_inverse_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
     from ..ops import trtrmm as _tm
-    from .exceptions import NLAError
-    if not isinstance(A, torch.Tensor) or A.layout != torch.strided or A.dim() != 2 or A.shape[0] != A.shape[1]:
-        raise DimensionMismatchError(
-            f"HPDInverse: A must be a dense square matrix (got {tuple(getattr(A, 'shape', ()))})")
+    _dense_square("HPDInverse", A)
     if _tm.takes(A):
         # the three native stages, in place on the one triangle; a pivot that
         # is not positive raises in Cholesky, before the other two run
@@ -708,18 +693,11 @@ def _hpd_inverse_local(up: str, A: torch.Tensor, info) -> torch.Tensor:
         if info is not None:
             info.zero_()
         return A
-    mask = _tri_mask(n, up, A.device)
-    S = torch.where(mask, A, torch.zeros((), dtype=A.dtype, device=A.device))
+    mask, S = _masked(A, up)
     Sh = S.t().conj() if S.is_complex() else S.t()
     S = S + Sh - torch.diag_embed(S.diagonal())          # the Hermitian matrix that the triangle stores
     F, linfo = torch.linalg.cholesky_ex(S, upper=up == "U")
-    if info is not None:
-        info.copy_(linfo.reshape(info.shape))
-    else:
-        p = int(linfo.item())
-        if p != 0:
-            raise NLAError(f"HPDInverse: the matrix is not positive definite: pivot {p} (1-based) "
-                           f"is not positive and finite")
+    _pivot_status("HPDInverse", linfo, info)
     A.copy_(torch.where(mask, torch.cholesky_inverse(F, upper=up == "U"), A))
     return A
 
@@ -747,16 +725,7 @@ def HPDInverse(uplo: str, A, info=None):
     the index (0: none) is left there without a host synchronisation and
     nothing is raised; on a non-zero status the triangle's contents are
     unspecified."""
-    up = str(uplo).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"uplo must be L or U (got {uplo})")
-    if _is_dist(A):
-        if A.layout != "STAR_STAR":
-            raise UnsupportedBaseOperation(f"HPDInverse of a {A.layout} matrix (only [*,*] and local)")
-        _hpd_inverse_local(up, A.local, info)
-        return A
-    _hpd_inverse_local(up, _as_tensor(A), info)
-    return A
+    return _tri_in_place("HPDInverse", _hpd_inverse_local, uplo, A, info)
 
 
 def ExplicitUnitary(A):

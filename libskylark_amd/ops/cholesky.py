@@ -17,11 +17,10 @@ import ctypes as C_
 
 import torch
 
-from . import _lib
+from . import _lib, _tri
 from ..base.exceptions import NLAError
 
 vp, i32, i64 = C_.c_void_p, C_.c_int, C_.c_int64
-_lib.register("sl_chol_tri_block", [C_.POINTER(C_.c_int), C_.POINTER(C_.c_int)])
 _lib.register("sl_chol_tri", [vp, i32, i64, i64, vp, vp])
 
 _WS: dict = {}
@@ -29,21 +28,8 @@ _WS: dict = {}
 
 def _why_not(A: torch.Tensor) -> str | None:
     # the device is checked last, so every other reason can be had (and tested) without a GPU
-    if not isinstance(A, torch.Tensor) or A.dim() != 2 or A.layout != torch.strided:
-        return "A must be a dense 2-D tensor"
-    if A.shape[0] != A.shape[1]:
-        return f"A must be square (got {tuple(A.shape)})"
-    if A.dtype != torch.float64:
-        return f"A must be f64 (got {A.dtype})"
-    if A.shape[1] > 1 and A.stride(1) != 1:
-        return "A must be row-major (unit column stride)"
-    if A.shape[0] > 1 and A.stride(0) < A.shape[1]:
-        return "A's rows overlap"
-    if A.data_ptr() % 8:
-        return "A needs an 8-B aligned base"
-    if not A.is_cuda:
-        return "A must be a CUDA tensor"
-    return None
+    return (_tri.why_not_square_f64(A, shape_first=True, row_major_only=True)
+            or (None if A.is_cuda else "A must be a CUDA tensor"))
 
 
 def takes(A: torch.Tensor) -> bool:
@@ -59,9 +45,7 @@ def ok(A: torch.Tensor) -> bool:
 
 def block() -> tuple[int, int]:
     """``(nb, T)``: the panel width and the edge of a trailing-update tile."""
-    nb, t = C_.c_int(0), C_.c_int(0)
-    _lib.call("sl_chol_tri_block", C_.byref(nb), C_.byref(t))
-    return nb.value, t.value
+    return _tri.block("sl_chol_tri_block", 2)
 
 
 def _status(A: torch.Tensor) -> torch.Tensor:
@@ -82,9 +66,7 @@ def chol_tri(A: torch.Tensor, uplo: str = "L", info: torch.Tensor | None = None)
     none), with no host synchronisation; the factor then holds NaN from that
     pivot on.  Without ``info`` the call reads its own status word (one
     synchronisation) and raises :class:`NLAError` naming the pivot."""
-    up = str(uplo).upper()
-    if up not in ("L", "U"):
-        raise ValueError(f"chol_tri: uplo must be L or U (got {uplo})")
+    up = _tri.flag(uplo, "uplo", "LU", "chol_tri")
     why = _why_not(A)
     if why is not None:
         raise ValueError(f"chol_tri: {why}")

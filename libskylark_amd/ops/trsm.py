@@ -20,10 +20,10 @@ import ctypes as C_
 
 import torch
 
-from . import _lib
+from . import _lib, _tri
+from ._tri import layout as _layout
 
 vp, i32, i64 = C_.c_void_p, C_.c_int, C_.c_int64
-_lib.register("sl_trsm_tri_block", [C_.POINTER(C_.c_int), C_.POINTER(C_.c_int), C_.POINTER(C_.c_int)])
 _lib.register("sl_trsm_tri", [vp, i32, i32, i32, i32, i64, i64, i64, vp, i64, vp])
 
 # Regimes that base.Trsm hands to the kernel ("thin": t <= block()[2], "wide":
@@ -36,21 +36,6 @@ _lib.register("sl_trsm_tri", [vp, i32, i32, i32, i32, i64, i64, i64, vp, i64, vp
 # sizes, both stay native.
 BASE_NATIVE_REGIMES = frozenset({"thin", "wide"})
 _THIN = 8           # sl_trsm_tri_block's third value (asserted in tests/test_gpu_trsm.py)
-
-
-def _layout(X: torch.Tensor):
-    """``("R" | "C", run, pitch)``: the unit-stride direction, the length of a
-    contiguous run and the distance between runs; a string when X has neither."""
-    r, c = X.shape
-    if c <= 1 or X.stride(1) == 1:
-        if r > 1 and X.stride(0) < c:
-            return "rows overlap"
-        return "R", c, (X.stride(0) if r > 1 else max(c, 1))
-    if r <= 1 or X.stride(0) == 1:
-        if c > 1 and X.stride(1) < r:
-            return "rows overlap"
-        return "C", r, (X.stride(1) if c > 1 else max(r, 1))
-    return "needs unit stride along rows or columns"
 
 
 def _span(X: torch.Tensor) -> int:
@@ -74,24 +59,17 @@ def _overlap(A: torch.Tensor, B: torch.Tensor) -> bool:
 
 def _why_not(side, A, B) -> str | None:
     # the device is checked last, so every other reason can be had (and tested) without a GPU
-    for nm, X in (("A", A), ("B", B)):
-        if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.layout != torch.strided:
-            return f"{nm} must be a dense 2-D tensor"
-    for nm, X in (("A", A), ("B", B)):
-        if X.dtype != torch.float64:
-            return f"{nm} must be f64 (got {X.dtype})"
-    if A.shape[0] != A.shape[1]:
-        return f"A must be square (got {tuple(A.shape)})"
+    why = (_tri.not_dense("A", A) or _tri.not_dense("B", B) or _tri.not_f64("A", A) or _tri.not_f64("B", B)
+           or _tri.not_square(A))
+    if why:
+        return why
     n = A.shape[0]
     if B.shape[0 if str(side).upper() == "L" else 1] != n:
         return f"B is {tuple(B.shape)}, side {side} needs {n} {'rows' if str(side).upper() == 'L' else 'columns'}"
-    for nm, X in (("A", A), ("B", B)):
-        lay = _layout(X)
-        if isinstance(lay, str):
-            return f"{nm}: {lay}" if lay.startswith("needs") else f"{nm}'s {lay}"
-    for nm, X in (("A", A), ("B", B)):
-        if X.data_ptr() % 8:
-            return f"{nm} needs an 8-B aligned base"
+    why = (_tri.bad_strides("A", A) or _tri.bad_strides("B", B) or _tri.misaligned("A", A)
+           or _tri.misaligned("B", B))
+    if why:
+        return why
     if A.device != B.device:
         return f"A is on {A.device}, B on {B.device}"
     if A.numel() and B.numel() and _overlap(A, B):
@@ -115,9 +93,7 @@ def ok(side, A, B) -> bool:
 def block() -> tuple[int, int, int]:
     """``(nb, T, thin)``: the diagonal block width, the edge of a wide-update
     tile and the largest number of right-hand sides of the thin regime."""
-    nb, t, th = C_.c_int(0), C_.c_int(0), C_.c_int(0)
-    _lib.call("sl_trsm_tri_block", C_.byref(nb), C_.byref(t), C_.byref(th))
-    return nb.value, t.value, th.value
+    return _tri.block("sl_trsm_tri_block", 3)
 
 
 def regime(side, B: torch.Tensor) -> str:
@@ -126,15 +102,8 @@ def regime(side, B: torch.Tensor) -> str:
 
 
 def _flags(side, uplo, orient, diag):
-    s, u, o, d = str(side).upper(), str(uplo).upper(), str(orient).upper(), str(diag).upper()
-    if s not in ("L", "R"):
-        raise ValueError(f"trsm_tri: side must be L or R (got {side})")
-    if u not in ("L", "U"):
-        raise ValueError(f"trsm_tri: uplo must be L or U (got {uplo})")
-    if o not in ("N", "T", "C"):
-        raise ValueError(f"trsm_tri: orient must be N, T or C (got {orient})")
-    if d not in ("N", "U"):
-        raise ValueError(f"trsm_tri: diag must be N or U (got {diag})")
+    s, u = _tri.flag(side, "side", "LR", "trsm_tri"), _tri.flag(uplo, "uplo", "LU", "trsm_tri")
+    o, d = _tri.flag(orient, "orient", "NTC", "trsm_tri"), _tri.flag(diag, "diag", "NU", "trsm_tri")
     return s, u, ("N" if o == "N" else "T"), d      # C is T for real data
 
 
@@ -155,13 +124,8 @@ def trsm_tri(side, uplo, orient, diag, alpha, A: torch.Tensor, B: torch.Tensor) 
         return B
     if alpha != 1:
         B.mul_(alpha)
-    An, Bn = A, B
-    if _layout(A)[0] == "C":
-        # a column-major A is the row-major transpose: the other triangle, the other orientation
-        An, u, o = A.t(), ("U" if u == "L" else "L"), ("T" if o == "N" else "N")
-    if _layout(B)[0] == "C":
-        # a column-major B is the row-major B^T: op(A) X = B is X^T op(A)^T = B^T
-        Bn, s, o = B.t(), ("R" if s == "L" else "L"), ("T" if o == "N" else "N")
+    An, u, o = _tri.row_major(A, (u, "LU"), (o, "NT"))
+    Bn, s, o = _tri.row_major(B, (s, "LR"), (o, "NT"))      # op(A) X = B is X^T op(A)^T = B^T
     _lib.call("sl_trsm_tri", _lib.ptr(An), ord(s), ord(u), ord(o), ord(d), n, t, _layout(An)[2], _lib.ptr(Bn),
               _layout(Bn)[2], vp(_lib.stream_of(B)))
     return B

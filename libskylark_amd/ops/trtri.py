@@ -20,44 +20,14 @@ import ctypes as C_
 
 import torch
 
-from . import _lib
+from . import _lib, _tri
 
 vp, i32, i64 = C_.c_void_p, C_.c_int, C_.c_int64
-_lib.register("sl_trtri_tri_block", [C_.POINTER(C_.c_int), C_.POINTER(C_.c_int)])
 _lib.register("sl_trtri_tri", [vp, i32, i32, i64, i64, vp])
 
 
-def _layout(A: torch.Tensor):
-    """``("R" | "C", pitch)``: the unit-stride direction and the distance
-    between rows (columns); a string when A has neither or its rows overlap."""
-    n = A.shape[0]
-    if n <= 1 or A.stride(1) == 1:
-        if n > 1 and A.stride(0) < n:
-            return "rows overlap"
-        return "R", (A.stride(0) if n > 1 else max(n, 1))
-    if A.stride(0) == 1:
-        if A.stride(1) < n:
-            return "rows overlap"
-        return "C", A.stride(1)
-    return "needs unit stride along rows or columns"
-
-
 def _why_not(A) -> str | None:
-    # the device is checked last, so every other reason can be had (and tested) without a GPU
-    if not isinstance(A, torch.Tensor) or A.dim() != 2 or A.layout != torch.strided:
-        return "A must be a dense 2-D tensor"
-    if A.dtype != torch.float64:
-        return f"A must be f64 (got {A.dtype})"
-    if A.shape[0] != A.shape[1]:
-        return f"A must be square (got {tuple(A.shape)})"
-    lay = _layout(A)
-    if isinstance(lay, str):
-        return f"A: {lay}" if lay.startswith("needs") else f"A's {lay}"
-    if A.data_ptr() % 8:
-        return "A needs an 8-B aligned base"
-    if not A.is_cuda:
-        return "A must be a CUDA tensor"
-    return None
+    return _tri.why_not_square_f64(A) or (None if A.is_cuda else "A must be a CUDA tensor")
 
 
 def takes(A) -> bool:
@@ -73,9 +43,7 @@ def ok(A) -> bool:
 
 def block() -> tuple[int, int]:
     """``(nb, T)``: the diagonal block width and the edge of an update tile."""
-    nb, t = C_.c_int(0), C_.c_int(0)
-    _lib.call("sl_trtri_tri_block", C_.byref(nb), C_.byref(t))
-    return nb.value, t.value
+    return _tri.block("sl_trtri_tri_block", 2)
 
 
 def launches(n: int, nb: int = 64) -> int:
@@ -84,28 +52,16 @@ def launches(n: int, nb: int = 64) -> int:
     return 0 if n == 0 else max(1, 3 * k - 2)
 
 
-def _flags(uplo, diag):
-    u, d = str(uplo).upper(), str(diag).upper()
-    if u not in ("L", "U"):
-        raise ValueError(f"trtri_tri: uplo must be L or U (got {uplo})")
-    if d not in ("N", "U"):
-        raise ValueError(f"trtri_tri: diag must be N or U (got {diag})")
-    return u, d
-
-
 def trtri_tri(uplo, diag, A: torch.Tensor) -> torch.Tensor:
     """Overwrite the ``uplo`` triangle of ``A`` with that of ``A^-1``; returns
     ``A``.  Diag U: the diagonal is taken as ones and neither read nor written."""
-    u, d = _flags(uplo, diag)
+    u, d = _tri.flag(uplo, "uplo", "LU", "trtri_tri"), _tri.flag(diag, "diag", "NU", "trtri_tri")
     why = _why_not(A)
     if why is not None:
         raise ValueError(f"trtri_tri: {why}")
     n = A.shape[0]
     if n == 0:
         return A
-    An = A
-    if _layout(A)[0] == "C":
-        # a column-major A is the row-major transpose: the other triangle, and (A^T)^-1 = (A^-1)^T
-        An, u = A.t(), ("U" if u == "L" else "L")
-    _lib.call("sl_trtri_tri", _lib.ptr(An), ord(u), ord(d), n, _layout(An)[1], vp(_lib.stream_of(A)))
+    An, u = _tri.row_major(A, (u, "LU"))      # (A^T)^-1 = (A^-1)^T
+    _lib.call("sl_trtri_tri", _lib.ptr(An), ord(u), ord(d), n, _tri.layout(An)[2], vp(_lib.stream_of(A)))
     return A

@@ -19,33 +19,18 @@ import ctypes as C_
 
 import torch
 
-from . import _lib
-from .trtri import _layout
+from . import _lib, _tri
 
 vp, i32, i64 = C_.c_void_p, C_.c_int, C_.c_int64
 MAX_PITCH = 1 << 22      # the kernel's offsets inside a 128 x 128 block are 32-bit byte offsets
-_lib.register("sl_trtrmm_tri_block", [C_.POINTER(C_.c_int), C_.POINTER(C_.c_int)])
 _lib.register("sl_trtrmm_tri", [vp, i32, i64, i64, vp])
 
 
 def _why_not(A) -> str | None:
-    # the device is checked last, so every other reason can be had (and tested) without a GPU
-    if not isinstance(A, torch.Tensor) or A.dim() != 2 or A.layout != torch.strided:
-        return "A must be a dense 2-D tensor"
-    if A.dtype != torch.float64:
-        return f"A must be f64 (got {A.dtype})"
-    if A.shape[0] != A.shape[1]:
-        return f"A must be square (got {tuple(A.shape)})"
-    lay = _layout(A)
-    if isinstance(lay, str):
-        return f"A: {lay}" if lay.startswith("needs") else f"A's {lay}"
-    if A.data_ptr() % 8:
-        return "A needs an 8-B aligned base"
-    if lay[1] > MAX_PITCH:
-        return f"A's pitch exceeds {MAX_PITCH} elements"
-    if not A.is_cuda:
-        return "A must be a CUDA tensor"
-    return None
+    why = _tri.why_not_square_f64(A)
+    if why is None and _tri.layout(A)[2] > MAX_PITCH:
+        why = f"A's pitch exceeds {MAX_PITCH} elements"
+    return why or (None if A.is_cuda else "A must be a CUDA tensor")
 
 
 def takes(A) -> bool:
@@ -61,9 +46,7 @@ def ok(A) -> bool:
 
 def block() -> tuple[int, int]:
     """``(nb, T)``: the height of a row slab and the edge of a tile."""
-    nb, t = C_.c_int(0), C_.c_int(0)
-    _lib.call("sl_trtrmm_tri_block", C_.byref(nb), C_.byref(t))
-    return nb.value, t.value
+    return _tri.block("sl_trtrmm_tri_block", 2)
 
 
 def launches(n: int, nb: int = 128) -> int:
@@ -72,26 +55,16 @@ def launches(n: int, nb: int = 128) -> int:
     return 0 if n == 0 else 2 * -(-n // nb) - 1
 
 
-def _flag(uplo):
-    u = str(uplo).upper()
-    if u not in ("L", "U"):
-        raise ValueError(f"trtrmm_tri: uplo must be L or U (got {uplo})")
-    return u
-
-
 def trtrmm_tri(uplo, A: torch.Tensor) -> torch.Tensor:
     """Overwrite the ``uplo`` triangle of ``A`` with that of ``L^T L`` (L) or
     ``U U^T`` (U); returns ``A``."""
-    u = _flag(uplo)
+    u = _tri.flag(uplo, "uplo", "LU", "trtrmm_tri")
     why = _why_not(A)
     if why is not None:
         raise ValueError(f"trtrmm_tri: {why}")
     n = A.shape[0]
     if n == 0:
         return A
-    An = A
-    if _layout(A)[0] == "C":
-        # a column-major A is the row-major transpose: the other triangle, and (L^T L)^T = U U^T with U = L^T
-        An, u = A.t(), ("U" if u == "L" else "L")
-    _lib.call("sl_trtrmm_tri", _lib.ptr(An), ord(u), n, _layout(An)[1], vp(_lib.stream_of(A)))
+    An, u = _tri.row_major(A, (u, "LU"))      # (L^T L)^T = U U^T with U = L^T
+    _lib.call("sl_trtrmm_tri", _lib.ptr(An), ord(u), n, _tri.layout(An)[2], vp(_lib.stream_of(A)))
     return A
