@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(NT) k_colscale(T* __restrict__ Yv, int64_t ldy
   constexpr int RS = NT / KP;
   if (tx >= k) return;
   double sv = s[tx];
-  if (inv) sv = sv > 0.0 ? 1.0 / sv : 0.0;
+  if (inv) sv = sv != 0.0 ? 1.0 / sv : 0.0;
   for (int64_t r = (int64_t)blockIdx.x * RS + ty; r < m; r += (int64_t)gridDim.x * RS) {
     T* y = Yv + r * ldy + tx;
     *y = Cvt<T>::from_d(sv * ld_d(y));
