@@ -408,7 +408,12 @@ def _herk_local(uplo: str, trans: bool, alpha, A: torch.Tensor, beta, C: torch.T
         beta = 0.0
     elif C.dim() != 2 or tuple(C.shape) != (s, s):
         raise DimensionMismatchError(f"Herk: C is {tuple(C.shape)}, op(A) op(A)^T is {(s, s)}")
-    from ..ops import syrk
+    from ..ops import herk, syrk
+    if (A.dtype == torch.float64 and A.is_cuda and ("T" if trans else "N") in herk.BASE_NATIVE_REGIMES
+            and herk.takes(A, C, trans=trans)):
+        # f64 GPU operands the kernel takes (C f64 on A's device): the native
+        # library is mandatory there (ops/_lib.py), a missing one raises
+        return herk.herk_tri(uplo, "T" if trans else "N", alpha, A, beta, C)
     An, tn = A, trans
     if A.is_cuda and k > 0 and s > 0:
         if A.dtype == torch.float32 and A.stride(1) != 1:
@@ -438,7 +443,13 @@ def Herk(uplo: str, orient: str, alpha, A, beta=0.0, C=None):
 
     f32 A on the GPU (either orientation) and bf16 A on the GPU with orient N
     run the native triangular kernel (``ops/syrk.py``: exact bf16-split
-    products, f64 across row chunks); every other local case is a torch
+    products, f64 across row chunks).  f64 A on the GPU with an f64 C on the
+    same device (or none), each with unit stride along rows or columns, runs
+    the native one-triangle kernel on the f64 matrix cores (``ops/herk.py``,
+    ``herk_tri.hip``): half the flops of the product, no s x s temporary, the
+    other triangle of C never read, ``beta == 0`` reads nothing of C,
+    bit-identical from run to run.  Every other local case (CPU, complex,
+    sparse, f64 A with an f32 C, views with neither unit stride) is a torch
     product in the operand's precision written through a triangle mask.
     ``[VC,*]`` A with orient T: local Herk + one all-reduce of the s x s
     block, replicated result; other distributed layouts are gathered."""

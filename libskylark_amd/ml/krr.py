@@ -204,9 +204,16 @@ def _ridge(Z: torch.Tensor, Y: torch.Tensor, lam: float, data: _Data | None = No
         G[:, s:] = normal_eq.dual(Z, Y2.to(torch.float32).contiguous())[0].double()
     else:
         chunk = max(1, (1 << 27) // max(1, s + t))
+        # opt-in, as on the split branch: the lower triangle of the f64 Gram
+        # only, accumulated chunk by chunk in the view of G (base.Herk: the
+        # native one-triangle f64 kernel on the GPU)
+        tri = not split and Z.is_cuda and os.environ.get("SKH_KRR_GRAM", "") == "syrk"
         for r0 in range(0, Z.shape[0], chunk):
             Zc = Z[r0:r0 + chunk].to(torch.float64)
-            if not split:
+            if tri:
+                from ..base.blas import Herk
+                Herk("L", "T", 1.0, Zc, 1.0, G[:, :s])
+            elif not split:
                 G[:, :s].addmm_(Zc.t(), Zc)
             G[:, s:].addmm_(Zc.t(), Y2[r0:r0 + chunk].to(torch.float64))
     if data is not None:
